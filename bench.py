@@ -11,11 +11,14 @@ reference's dense collate tensors, all graph-conv layers forward, read-out + hea
 full backward (gradients of every parameter), and for N > 1 the gradient all-reduce.  The optimizer
 is excluded.  Weak scaling: every rank processes its own batch of `--batch` molecules.
 
-Timing: after W warm-up steps, R blocks of exactly K steps each are timed (barrier + synchronize on both
-sides of every block, MAX over ranks); `ms_per_step` / `value` are the MEDIAN block, `value_min` /
-`value_max` the slowest / fastest block.  Rank 0 prints ONE JSON line.  At N = 1 the line also carries
-`extra`: the same measurement for the north-star shape (Tox21, batch 1024) and the other BASELINE.json
-configs that fit one GPU, each with its whole-step fraction of the fp32-MFMA roofline.
+Timing: after W warm-up steps, exactly K steps are timed, in R blocks (`--repeats`; default: up to 5 blocks
+of at least 50 steps each, so that K < 100 is one block) that split the K steps as evenly as possible (barrier + synchronize on both sides of every block, MAX over ranks);
+`ms_per_step` / `value` are the MEDIAN block's time per step, `value_min` / `value_max` the slowest /
+fastest block's.  `--dump-outputs DIR` writes what the last timed step computed (loss, outputs, graph
+representation, a seeded sample of the atom representations, every parameter gradient) as DIR/<name>.npy.
+Rank 0 prints ONE JSON line.  At N = 1 the line also carries `extra`: the same measurement for the
+north-star shape (Tox21, batch 1024) and the other BASELINE.json configs that fit one GPU,
+each with its whole-step fraction of the fp32-MFMA roofline.
 """
 import argparse
 import ctypes as C
@@ -23,6 +26,8 @@ import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -230,8 +235,54 @@ def cpu_baseline(cfg, mb, dropout, bce_w, steps=5, warmup=2, threads=None, sweep
                          model_name or 'unknown CPU')}
 
 
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs: at most this much in all
+DUMP_ARRAY_BYTES = 16 << 20          # a larger array is stored as a fixed, seeded sample of this size
+
+
+BLOCKS_DEFAULT, BLOCK_MIN_STEPS = 5, 50    # --repeats not given: up to 5 blocks, none shorter than 50 steps
+
+
+def block_sizes(steps, repeats):
+    """The `steps` timed steps split into min(repeats, steps) blocks as evenly as possible (repeats None: the default)."""
+    if repeats is None:
+        repeats = min(BLOCKS_DEFAULT, steps // BLOCK_MIN_STEPS)
+    n = max(1, min(repeats, steps))
+    return [steps // n + (1 if i < steps % n else 0) for i in range(n)]
+
+
+def host_outputs(model, loss, outs):
+    """What a caller of the timed step receives, copied to the host at once (the step's buffers are static and reused):
+    {name: float32 / float64 numpy array}.  An array above DUMP_ARRAY_BYTES is a fixed, seeded sample of its elements."""
+    out, atom_rep, graph_rep = outs
+    arrays = [('loss', loss), ('out', out), ('graph_representation', graph_rep)]
+    if atom_rep is not None:
+        arrays.append(('atom_representations', atom_rep.cpu() if hasattr(atom_rep, 'cpu') else atom_rep))
+    arrays += [('grad.' + k, p.grad) for k, p in model.named_parameters() if p.grad is not None]
+    res = {}
+    for name, t in arrays:
+        if not isinstance(t, torch.Tensor):
+            continue
+        a = t.detach().cpu()
+        a = (a if a.dtype == torch.float64 else a.float()).numpy()
+        if a.nbytes > DUMP_ARRAY_BYTES:
+            keep = DUMP_ARRAY_BYTES // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a, name = a.reshape(-1)[idx], name + '.sample'
+        res[name] = np.ascontiguousarray(a)
+    return res
+
+
+def dump_outputs(d, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + '.npy'), a)
+
+
 def run_workload(name, B, args, lib, dev, rank, world, reducer_cls, detail):
-    """Build the model and one resident batch, time R blocks of K steps.  Returns a dict (timings are the MAX over
+    """Build the model and one resident batch, time K steps in R blocks.  Returns a dict (timings are the MAX over
     ranks); with `detail` also the per-kernel-class HIP-event durations of eager steps of the same workload."""
     from eagcn_amd.losses import fused_classification_loss, fused_regression_loss
     from eagcn_amd.synthetic import bce_weights, make_batch
@@ -247,6 +298,7 @@ def run_workload(name, B, args, lib, dev, rank, world, reducer_cls, detail):
     labelss = [torch.from_numpy(m_.labels).to(dev) for m_ in mbs]
     dense, compact, labels = denses[0], compacts[0], labelss[0]
     counter = [0]
+    last = [None]                   # (out, atom_rep, graph_rep) of the latest step
     bce_w = bce_weights(cfg['nclass'])
     bce_w_dev = torch.tensor(bce_w, dtype=torch.float32, device=dev)
     model = build_model(cfg, args.dropout, dev, graph=not args.eager)
@@ -277,13 +329,14 @@ def run_workload(name, B, args, lib, dev, rank, world, reducer_cls, detail):
             # more than one rank the gradient average is captured INTO that graph (upper bucket beside the first layer's
             # backward) and the global BCE normalisation is a 1-element collective issued with the batch preparation
             batch = dense if compact is None else (compact[1], compact[2])
-            loss, _ = model.fused_step(batch, labels, cfg['task'], bce_w_dev, 'dp' if (world > 1 and cfg['task'] == 'class') else None,
+            loss, last[0] = model.fused_step(batch, labels, cfg['task'], bce_w_dev, 'dp' if (world > 1 and cfg['task'] == 'class') else None,
                                        bonds=None if compact is None else compact[0], reducer=reducer if world > 1 else None,
                                        **({'optimizer': optimizer} if opt_kind == 'flat' else {}))
             if opt_kind == 'torch':
                 optimizer.step()
             return loss
-        out, _, _ = model(*dense) if compact is None else model.forward_compact(*compact)
+        last[0] = model(*dense) if compact is None else model.forward_compact(*compact)
+        out = last[0][0]
         if cfg['task'] == 'class':
             loss = fused_classification_loss(out, labels, bce_w_dev, dp_global_norm=(world > 1))
         else:
@@ -305,14 +358,15 @@ def run_workload(name, B, args, lib, dev, rank, world, reducer_cls, detail):
     lib.eagcn_prof_reset()
     blocks = []
     loss = None
-    for r in range(args.repeats):
+    sizes = block_sizes(args.steps, args.repeats)
+    for nsteps in sizes:
         torch.cuda.synchronize()
         if dist.is_initialized():
             dist.barrier()
         lib.eagcn_prof_enable(1 if profile_in_loop else 0)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(nsteps):
             loss = step()
         torch.cuda.synchronize()
         if dist.is_initialized():
@@ -323,15 +377,16 @@ def run_workload(name, B, args, lib, dev, rank, world, reducer_cls, detail):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         if dist.is_initialized():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        blocks.append(float(t.item()))
+        blocks.append(float(t.item()) / nsteps)          # seconds per step of this block
     if not torch.isfinite(loss.detach()).item():
         raise SystemExit('non-finite loss')
-    res = {'cfg': cfg, 'mb': mb, 'bce_w': bce_w, 'B': B, 'blocks': sorted(blocks),
+    dumped = host_outputs(model, loss, last[0]) if (detail and rank == 0 and args.dump_outputs) else None
+    res = {'cfg': cfg, 'mb': mb, 'bce_w': bce_w, 'B': B, 'blocks': sorted(blocks), 'dumped': dumped,
            'gflop': algorithmic_flops(cfg, mb.sizes) / 1e9, 'N': mb.N, 'bytes': algorithmic_bytes(cfg, mb.sizes, mb.N),
            'moved': moved_bytes(cfg, mb),
            'rank_ms': None, 'allreduce': None}
     if dist.is_initialized() and world > 1:
-        mine = torch.tensor([sorted(blocks)[len(blocks) // 2] / args.steps * 1e3], dtype=torch.float64, device=dev)
+        mine = torch.tensor([sorted(blocks)[len(blocks) // 2] * 1e3], dtype=torch.float64, device=dev)
         every = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(every, mine)
         res['rank_ms'] = [round(float(t), 4) for t in every]
@@ -340,7 +395,7 @@ def run_workload(name, B, args, lib, dev, rank, world, reducer_cls, detail):
                             '+ head] started before the first layer\'s backward, bucket [layer 1] after it'
                             if (runner is not None and runner.comm_in_graph) else
                             'in-place AVG of the flat fp32 gradient buffer over RCCL, one host-issued collective after the step graph')
-    prof_steps = args.steps * args.repeats
+    prof_steps = args.steps
     if detail and not profile_in_loop:
         # per-kernel-class durations: the same step, same batch, eager launches with one HIP-event pair per
         # kernel class on the launch stream (the timed region above replays the identical kernels as graphs)
@@ -381,16 +436,16 @@ def run_workload(name, B, args, lib, dev, rank, world, reducer_cls, detail):
 
 
 def summarize(res, args, world):
-    """(value, ms_per_step, min, max, step_frac) of a run_workload result: median block."""
+    """(value, ms_per_step, min, max, step_frac) of a run_workload result: median block (`blocks`: seconds per step)."""
     b = res['blocks']
     med = b[len(b) // 2]
-    ms = med / args.steps * 1e3
-    value = world * res['B'] * args.steps / med
+    ms = med * 1e3
+    value = world * res['B'] / med
     dense_b, act_b = res['bytes']
     t_mfma = res['gflop'] / PEAK_FP32_MFMA_TFLOPS                     # ms at the fp32 MFMA peak
     t_hbm = (dense_b + act_b) / (PEAK_HBM_GBS * 1e6)                   # ms at 8 TB/s
     return {'value': round(value, 1), 'ms_per_step': round(ms, 4),
-            'value_min': round(world * res['B'] * args.steps / b[-1], 1), 'value_max': round(world * res['B'] * args.steps / b[0], 1),
+            'value_min': round(world * res['B'] / b[-1], 1), 'value_max': round(world * res['B'] / b[0], 1),
             'algorithmic_gflop_per_step': round(res['gflop'], 3),
             'step_tflops': round(res['gflop'] / ms, 2), 'step_frac': round(res['gflop'] / ms / PEAK_FP32_MFMA_TFLOPS, 4),
             # SURVEY.md 8(d): "report both numbers per config; relevant roofline = max(T_flops, T_bytes)"
@@ -404,9 +459,14 @@ def summarize(res, args, world):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=50)
+    ap.add_argument('--steps', type=int, default=50, help='timed steps (in all)')
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--repeats', type=int, default=15, help='timed blocks of --steps steps; the median block is reported')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='timed blocks the --steps steps are split into; the median block is reported (default: up to %d blocks of at '
+                         'least %d steps)' % (BLOCKS_DEFAULT, BLOCK_MIN_STEPS))
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (loss, outputs, graph representation, a seeded sample of the atom '
+                         'representations, every parameter gradient) as DIR/<name>.npy, float32 / float64, at most 64 MB in all')
     ap.add_argument('--workload', default='tox21_c2', choices=sorted(WORKLOADS))
     ap.add_argument('--batch', type=int, default=None, help='molecules per GPU (default: the config\'s)')
     ap.add_argument('--dropout', type=float, default=0.3)
@@ -429,6 +489,8 @@ def main():
     ap.add_argument('--input', default='dense', choices=('dense', 'compact'),
                     help="dense: the reference's collate tensors (headline); compact: bond list via forward_compact")
     args = ap.parse_args()
+    if args.steps < 1 or (args.repeats is not None and args.repeats < 1):
+        raise SystemExit('--steps and --repeats must be >= 1')
 
     if args.require_in_graph_allreduce:
         os.environ['EAGCN_REQUIRE_IN_GRAPH_ALLREDUCE'] = '1'      # (read by eagcn_amd.graph at import)
@@ -449,6 +511,9 @@ def main():
     B = args.batch or WORKLOADS[args.workload]['batch']
     res = run_workload(args.workload, B, args, lib, dev, rank, world, GradientAllReducer, detail=True)
     cfg, mb, kern = res['cfg'], res['mb'], res['kern']
+    if res['dumped'] is not None:
+        dump_outputs(args.dump_outputs, res['dumped'])
+        res['dumped'] = None
     out = None
     if rank == 0:
         head = summarize(res, args, world)
@@ -465,9 +530,10 @@ def main():
             'value': head['value'], 'unit': 'molecules/s', 'n_gpus': world, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': head['ms_per_step'], 'higher_is_better': True,
             'scaling': 'weak', 'vs_baseline': None, 'dtype': GEMM_MODES.get(gemm_mode, 'f32 (gemm mode %d)' % gemm_mode), 'data': 'synthetic',
-            'repeats': args.repeats, 'value_min': head['value_min'], 'value_max': head['value_max'],
-            'timing': 'median of %d timed blocks of %d steps each (barrier + synchronize around every block, max over ranks); '
-                      'value_min / value_max = slowest / fastest block' % (args.repeats, args.steps),
+            'repeats': len(res['blocks']), 'value_min': head['value_min'], 'value_max': head['value_max'],
+            'timing': '%d timed steps in %d block(s) of %s steps (barrier + synchronize around every block, max over ranks); median block\'s '
+                      'time per step; value_min / value_max = slowest / fastest block' % (args.steps, len(res['blocks']),
+                                                                                          '/'.join(str(n) for n in block_sizes(args.steps, args.repeats))),
             'config': {'workload': '%s: %s, %d-layer %d-view, widths %s/%s, %d tasks, batch %d per GPU, '
                                    'N_pad %d, dropout %.2f, loss %s' %
                                    (args.workload, cfg['structure'], cfg['n_layers'], len(cfg['widths1']),
@@ -549,7 +615,7 @@ def main():
                                                ('b1024_train_step', ('tox21_c2', 1024, 30, M))):
             del res
             torch.cuda.empty_cache()
-            args.repeats, args.steps, args.warmup = 5, steps, 4
+            args.repeats, args.steps, args.warmup = 5, 5 * steps, 4      # 5 blocks of `steps` steps
             args.rotate = 4 if key.endswith('rotate4') else 1
             args.optimizer = 'torch' if key.endswith('torch_adam') else ('flat' if 'train_step' in key else keep_opt)
             old_mode = lib.eagcn_set_gemm_mode(mode)         # fresh model + fresh graphs per workload: captured with this mode
@@ -558,7 +624,7 @@ def main():
             finally:
                 lib.eagcn_set_gemm_mode(old_mode)
             e = summarize(res, args, world)
-            e['workload'] = '%s, batch %d, N_pad %d, %d blocks of %d steps%s' % (wname, wb, res['N'], args.repeats, args.steps,
+            e['workload'] = '%s, batch %d, N_pad %d, %d blocks of %d steps%s' % (wname, wb, res['N'], args.repeats, args.steps // args.repeats,
                                                                                  ', 4 distinct resident batches round-robin (the side-stream index build reads fresh data every step)' if args.rotate > 1 else '')
             e['dtype'] = GEMM_MODES.get(mode, 'gemm mode %d' % mode)
             if mode == 4:
