@@ -212,6 +212,16 @@ SIGNATURES = {
                                        _fp, _fp, C.POINTER(LayerGrads), C.POINTER(HeadGrads), _fp]),
     'eagcn_model_backward_range': (C.c_int, [C.POINTER(Batch), C.POINTER(Model), _fp, _fp, C.c_size_t, _fp, C.c_size_t,
                                              _fp, _fp, C.POINTER(LayerGrads), C.POINTER(HeadGrads), C.c_int, C.c_int, C.c_int, _fp]),
+    'eagcn_model_input_scratch_bytes': (C.c_size_t, [C.POINTER(Batch), C.POINTER(Model)]),
+    'eagcn_model_backward_input': (C.c_int, [C.POINTER(Batch), C.POINTER(Model), _fp, _fp, C.c_size_t, _fp, C.c_size_t,
+                                             _fp, _fp, C.POINTER(LayerGrads), C.POINTER(HeadGrads), _fp, _fp]),
+    'eagcn_attr_alpha': (C.c_float, [C.c_int, C.c_int]),
+    'eagcn_attr_weight': (C.c_float, [C.c_int]),
+    'eagcn_attr_acc_elems': (C.c_size_t, [C.POINTER(Batch), C.POINTER(Model)]),
+    'eagcn_attr_pack_input': (C.c_int, [C.POINTER(Batch), C.POINTER(Model), _fp, _fp, C.c_float, _fp, C.c_size_t, _fp]),
+    'eagcn_attr_step': (C.c_int, [C.POINTER(Batch), C.POINTER(Model), _fp, _fp, C.c_size_t, _fp, C.c_size_t, _fp, _fp, C.c_float,
+                                  C.c_int, _fp, _fp]),
+    'eagcn_attr_finalize': (C.c_int, [C.POINTER(Batch), C.POINTER(Model), _fp, _fp, _fp, _fp, _fp, _fp]),
     'eagcn_model_forward_step': (C.c_int, [C.POINTER(Batch), C.POINTER(Model), _fp, _fp, _fp, C.c_size_t, _fp, C.c_size_t, _fp, _fp,
                                            C.POINTER(StepLoss), _fp, C.POINTER(HeadGrads), _fp]),
     'eagcn_head_saved_bytes': (C.c_size_t, [C.POINTER(HeadParams), C.c_int]),

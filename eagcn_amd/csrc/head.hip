@@ -677,14 +677,14 @@ extern "C" int eagcn_model_backward(const eagcn_batch* b, const eagcn_model* m, 
                                       m->n_layers - 1, 0, stream);
 }
 
-extern "C" int eagcn_model_backward_range(const eagcn_batch* b, const eagcn_model* m, const int64_t* size, void* saved,
-                                          size_t saved_bytes, void* scratch, size_t scratch_bytes, const float* dout,
-                                          const float* dgraph_rep, const eagcn_layer_grads* lg,
-                                          const eagcn_head_grads* hg, int with_head, int layer_hi, int layer_lo, void* stream) {
+// the layer / head backward of eagcn_model_backward_range and eagcn_model_backward_input: dx0 != null: layer 0 also forms d(its
+// input), packed [T][ld_in]; input_only: lg == null, no parameter gradient of a layer is formed (hg: the caller's throw-away buffers)
+static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const int64_t* size, void* saved, size_t saved_bytes,
+                               void* scratch, size_t scratch_bytes, const float* dout, const float* dgraph_rep,
+                               const eagcn_layer_grads* lg, const eagcn_head_grads* hg, int with_head, int layer_hi, int layer_lo,
+                               float* dx0, bool input_only, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    RC(check_model(b, m, "eagcn_model_backward"));
-    EAGCN_CHECK_GEMM3("eagcn_model_backward");
-    EAGCN_CHECK_ARG(saved && scratch && dout && lg && hg, "eagcn_model_backward: null buffer");
+    EAGCN_CHECK_ARG(saved && scratch && dout && (lg || input_only) && hg, "eagcn_model_backward: null buffer");
     EAGCN_CHECK_ARG(hg->d_den1_w && hg->d_den2_w && hg->d_den3_w && hg->d_gbn_w && hg->d_gbn_b && hg->d_bn1_w &&
                         hg->d_bn1_b && hg->d_bn2_w && hg->d_bn2_b, "eagcn_model_backward: null head gradient");
     EAGCN_CHECK_ARG(layer_hi < m->n_layers && layer_lo >= 0 && layer_lo <= layer_hi + 1,
@@ -707,7 +707,8 @@ extern "C" int eagcn_model_backward_range(const eagcn_batch* b, const eagcn_mode
     if (with_head) {
         const HeadPlan P = head_plan(b, m, sv, sc, nullptr, nullptr, dout, dgraph_rep, hg);
         RC(head_backward_launches(m, P, stream));
-        RC(readout_pad_backward(b, m, size, sv, sc, stream));
+        // (the gradient of the non-stored rows only enters the BatchNorm reductions, which the input-only form skips in eval mode)
+        if (!(input_only && !m->training)) RC(readout_pad_backward(b, m, size, sv, sc, stream));
     }
     ReadoutGrad rgd;
     memset(&rgd, 0, sizeof(rgd));
@@ -715,6 +716,7 @@ extern "C" int eagcn_model_backward_range(const eagcn_batch* b, const eagcn_mode
     const int top_l = m->n_layers - 1;
     EdgeDrain pend_in, pend_out;
     pend_in.eacc = nullptr;
+    pend_out.eacc = nullptr;                                     // (the input-only form hands no edge reduction down)
     for (int l = layer_hi; l >= layer_lo; --l) {
         // d(layer input) ping-pongs between two buffers, top-down: the layer t = top - l below the top reads the buffer the
         // layer above wrote (t odd: dxb, t even: dxa) and writes the other one
@@ -735,13 +737,98 @@ extern "C" int eagcn_model_backward_range(const eagcn_batch* b, const eagcn_mode
         // (a layer that has only its edge-gradient reduction left hands it to the next layer's first kernel -- if one follows in
         //  this call)
         RC(layer_backward_impl(b, &m->layer[l], &w, top ? nullptr : cur, top ? &rgd : nullptr, dpad,
-                               l > 0 ? other : nullptr, &lg[l], stream, top && sampled, top ? &zb : nullptr,
-                               pend_in.eacc ? &pend_in : nullptr, l > layer_lo ? &pend_out : nullptr));
+                               l > 0 ? other : dx0, input_only ? nullptr : &lg[l], stream, top && sampled, top ? &zb : nullptr,
+                               pend_in.eacc ? &pend_in : nullptr, (l > layer_lo && !input_only) ? &pend_out : nullptr, input_only));
         pend_in = pend_out;
         if (l == layer_lo) pend_in.eacc = nullptr;
     }
     if (forked) RC(stream_after(s, side));                       // join: every gradient is complete on s
     return EAGCN_OK;
+}
+
+extern "C" int eagcn_model_backward_range(const eagcn_batch* b, const eagcn_model* m, const int64_t* size, void* saved,
+                                          size_t saved_bytes, void* scratch, size_t scratch_bytes, const float* dout,
+                                          const float* dgraph_rep, const eagcn_layer_grads* lg,
+                                          const eagcn_head_grads* hg, int with_head, int layer_hi, int layer_lo, void* stream) {
+    RC(check_model(b, m, "eagcn_model_backward"));
+    EAGCN_CHECK_GEMM3("eagcn_model_backward");
+    return model_backward_impl(b, m, size, saved, saved_bytes, scratch, scratch_bytes, dout, dgraph_rep, lg, hg, with_head, layer_hi,
+                               layer_lo, nullptr, false, stream);
+}
+
+// ---- d / d afm (eagcn_model_backward_input, attribution) -------------------------------------------------------------------------------
+// scratch of the input backward: the model scratch, then layer 0's packed d(input) [T][ld_in], then the head's weight gradients of the
+// input-only form (formed by the head's backward kernels and discarded)
+struct InputScratch { float* dx0; eagcn_head_grads hg; };
+static size_t carve_input_scratch(void* base, const eagcn_batch* b, const eagcn_model* m, InputScratch* out) {
+    Carver2 c(base);
+    c.off = carve_scratch(nullptr, b, m, nullptr);
+    InputScratch t;
+    const eagcn_head_params* h = &m->head;
+    const size_t F = h->f_in, n1 = h->n_den1, n2 = h->n_den2, nc = h->nclass;
+    t.dx0 = c.take<float>((size_t)std::max(b->T, 1) * layout_ld(&m->layer[0].in));
+    t.hg.d_den1_w = c.take<float>(F * n1);
+    t.hg.d_den2_w = c.take<float>(n1 * n2);
+    t.hg.d_den3_w = c.take<float>(n2 * nc);
+    t.hg.d_gbn_w = c.take<float>(F);
+    t.hg.d_gbn_b = c.take<float>(F);
+    t.hg.d_bn1_w = c.take<float>(n1);
+    t.hg.d_bn1_b = c.take<float>(n1);
+    t.hg.d_bn2_w = c.take<float>(n2);
+    t.hg.d_bn2_b = c.take<float>(n2);
+    if (out) *out = t;
+    return c.off;
+}
+
+// structures the model engine runs (GAT and Diff_Pooling models form their fingerprints through layer-level ops: no engine batch)
+static int check_engine_model(const eagcn_batch* b, const eagcn_model* m, const char* who) {
+    RC(check_model(b, m, who));
+    EAGCN_CHECK_ARG(m->molfp_mode == 0 || m->molfp_mode == 1, "%s: read-out mode %d has no engine path", who, m->molfp_mode);
+    for (int l = 0; l < m->n_layers; ++l)
+        EAGCN_CHECK_ARG(m->layer[l].structure == EAGCN_STRUCT_CONCATE || m->layer[l].structure == EAGCN_STRUCT_WEIGHTED,
+                        "%s: layer %d has structure %d, which the engine does not run", who, l, m->layer[l].structure);
+    return EAGCN_OK;
+}
+
+int eagcn::model_backward_input_packed(const eagcn_batch* b, const eagcn_model* m, const int64_t* size, void* saved, size_t saved_bytes,
+                                       void* scratch, size_t scratch_bytes, const float* dout, const float* dgraph_rep,
+                                       const eagcn_layer_grads* lg, const eagcn_head_grads* hg, float** dx0, void* stream,
+                                       const char* who) {
+    // (arguments are checked before any HIP call)
+    EAGCN_CHECK_ARG(b && m, "%s: null argument", who);
+    EAGCN_CHECK_ARG((lg == nullptr) == (hg == nullptr), "%s: lg and hg are both given (full backward) or both NULL (input-only)", who);
+    RC(check_engine_model(b, m, who));
+    EAGCN_CHECK_GEMM3(who);
+    EAGCN_CHECK_ARG(saved && scratch && dout, "%s: null buffer", who);
+    InputScratch is;
+    EAGCN_CHECK_ARG(carve_input_scratch(scratch, b, m, &is) <= scratch_bytes, "%s: scratch too small (eagcn_model_input_scratch_bytes)", who);
+    *dx0 = is.dx0;
+    const bool input_only = lg == nullptr;
+    return model_backward_impl(b, m, size, saved, saved_bytes, scratch, scratch_bytes, dout, dgraph_rep, lg, input_only ? &is.hg : hg, 1,
+                               m->n_layers - 1, 0, is.dx0, input_only, stream);
+}
+
+int eagcn::model_input_slot(const eagcn_batch* b, const eagcn_model* m, void* saved, size_t saved_bytes, float** x0, const char* who) {
+    ModelSaved sv;
+    EAGCN_CHECK_ARG(carve_saved(saved, b, m, &sv) <= saved_bytes, "%s: saved block too small", who);
+    *x0 = sv.x0;
+    return EAGCN_OK;
+}
+
+extern "C" size_t eagcn_model_input_scratch_bytes(const eagcn_batch* b, const eagcn_model* m) {
+    return (b && m) ? carve_input_scratch(nullptr, b, m, nullptr) : 0;
+}
+
+extern "C" int eagcn_model_backward_input(const eagcn_batch* b, const eagcn_model* m, const int64_t* size, void* saved,
+                                          size_t saved_bytes, void* scratch, size_t scratch_bytes, const float* dout,
+                                          const float* dgraph_rep, const eagcn_layer_grads* lg, const eagcn_head_grads* hg,
+                                          float* dafm, void* stream) {
+    EAGCN_CHECK_ARG(dafm, "eagcn_model_backward_input: null dafm");
+    float* dx0 = nullptr;
+    RC(model_backward_input_packed(b, m, size, saved, saved_bytes, scratch, scratch_bytes, dout, dgraph_rep, lg, hg, &dx0, stream,
+                                   "eagcn_model_backward_input"));
+    // packed rows -> dense [B][N][n_afeat] (the caller's row stride, as eagcn_model_pack_input reads it): rows that are not stored are 0
+    return launch_attr_dense(b, &m->layer[0].in, dx0, nullptr, nullptr, dafm, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int eagcn_stream_signal_flag(uint32_t* flag, void* stream) {

@@ -17,6 +17,10 @@ struct AggArgs {
     int nchunk;
     int cpw = 1;                 // lagg.hip: consecutive 32-column chunks a workgroup takes per block (nchunk then counts chunk GROUPS)
     int xcd = 0;                 // wave-per-tile variant: tiles handed out so that an XCD works on CONTIGUOUS tiles (agg.hip)
+    // input-only backward, Concate layer in eval mode (lagg_in.hip, with w_aw set): `src` is the upstream gradient at the PACKED column and
+    // dH = src m_i [relu'(sc Y' + sh) > 0] (bn_bwd_reduce_kernel<false,...> with c1 = c2 = 0); w_aw is not read then.  (Here, in the
+    // padding in front of `planes`: the argument block of the other forms keeps its layout)
+    bool w_rowm = false;
     BxOut planes = {nullptr, 0, 0, 0};   // transposed: dP leaves as bf16 planes INSTEAD of the fp32 matrix (only the plane GEMMs read it)
     // transposed, lagg.hip only: `src` holds dH (the BatchNorm's upstream gradient), not dY': the BatchNorm backward's second pass
     //     dY' = sc (dH - c1 - (Y' - mu) inv c2)      (layer.hip bn_bwd_apply_kernel)
@@ -42,7 +46,10 @@ bool lagg_wanted(int B, int N, int structure);
 int lagg_block_rows(const eagcn_batch* b);     // rows per row block for batches of this shape (index_blocks_kernel; <= LAGG_RB)
 int lagg_slabs(const eagcn_batch* b);        // capacity of its BatchNorm partial slabs (one per row block; meta[NBLK] of them are live)
 int launch_lagg_fwd(AggArgs a, hipStream_t s);
-int launch_lagg_bwd(AggArgs a, const EdgeArgs& e, hipStream_t s);   // transposed aggregation + edge gradients (e.atomic must be set)
+// transposed aggregation + edge gradients (e.atomic must be set); edge = false: the aggregation alone (input-only backward)
+int launch_lagg_bwd(AggArgs a, const EdgeArgs& e, hipStream_t s, bool edge = true);
+// lagg_in.hip: the edge = false instantiations, on the grid launch_lagg_bwd computed
+int launch_lagg_bwd_input(const AggArgs& a, const EdgeArgs& e, dim3 grid, hipStream_t s);
 
 struct EdgeArgs {
     eagcn_batch bt;
@@ -255,7 +262,19 @@ struct EdgeDrain {
 int layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w,
                         const float* dxout, const ReadoutGrad* rg, const float* dpad_row, float* dx,
                         const eagcn_layer_grads* g, void* stream, bool dpad_views = false,
-                        const ZeroJob* zero_after = nullptr, const EdgeDrain* drain_in = nullptr, EdgeDrain* drain_out = nullptr);
+                        const ZeroJob* zero_after = nullptr, const EdgeDrain* drain_in = nullptr, EdgeDrain* drain_out = nullptr,
+                        bool input_only = false);
+// model engine (head.hip): the backward of eagcn_model_backward_input with layer 0's d(input) left PACKED ([T][ld_in] inside the scratch
+// block, *dx0), and where the packed input lives inside `saved` (attr.hip)
+int model_backward_input_packed(const eagcn_batch* b, const eagcn_model* m, const int64_t* size, void* saved, size_t saved_bytes,
+                                void* scratch, size_t scratch_bytes, const float* dout, const float* dgraph_rep,
+                                const eagcn_layer_grads* lg, const eagcn_head_grads* hg, float** dx0, void* stream, const char* who);
+// attr.hip: dense [B][N][F] from packed rows acc [T][ld] of layout `in`, times (x - base) when x != null; score[b][i] = row sums or null
+int launch_attr_dense(const eagcn_batch* b, const eagcn_layout* in, const float* acc, const float* x, const float* base, float* attr,
+                      float* score, hipStream_t s);
+int model_input_slot(const eagcn_batch* b, const eagcn_model* m, void* saved, size_t saved_bytes, float** x0, const char* who);
+// input_only: d(layer input) alone -- g may be null, no parameter gradient is formed (no dW product, no edge gradients, no gradient
+// unpacking; in eval mode no BatchNorm reduction either: dY' = sc dH is formed where the transposed aggregation stages its rows)
 // skip_apply: stop after the BatchNorm table (the caller applies it while it consumes Y: fused read-out of the top layer)
 // planes_only: the output leaves as the operand planes of the next layer's products ONLY (w->xout_planes; the fp32 matrix w->xout
 // is not written): the model engine asks for it when layer_reads_planes_only() holds for the layer above

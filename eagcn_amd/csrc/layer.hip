@@ -1222,16 +1222,19 @@ extern "C" int eagcn_layer_backward(const eagcn_batch* b, const eagcn_layer_para
 int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w,
                                const float* dxout, const ReadoutGrad* rg, const float* dpad_row, float* dx,
                                const eagcn_layer_grads* g, void* stream, bool dpad_views, const ZeroJob* zero_after,
-                               const EdgeDrain* drain_in, EdgeDrain* drain_out) {
+                               const EdgeDrain* drain_in, EdgeDrain* drain_out, bool input_only) {
     if (drain_out) drain_out->eacc = nullptr;
     hipStream_t s = (hipStream_t)stream;
     int rc = check_layer(b, p, "eagcn_layer_backward");
     if (rc) return rc;
-    EAGCN_CHECK_ARG(w && g && w->bn && w->scratch, "eagcn_layer_backward: null buffer");
-    EAGCN_CHECK_ARG(b->T == 0 || ((dxout || rg) && (w->x || w->x_planes) && w->P && w->Y && w->rscale), "eagcn_layer_backward: null activation buffer");
-    for (int k = 0; k < p->K; ++k)
-        EAGCN_CHECK_ARG(g->dW[k] && g->dbias[k] && g->dgamma[k] && g->dbeta[k] && g->datt_w[k] && g->dself_r[k],
-                        "eagcn_layer_backward: view %d has a null gradient buffer", k);
+    EAGCN_CHECK_ARG(w && (g || input_only) && w->bn && w->scratch, "eagcn_layer_backward: null buffer");
+    EAGCN_CHECK_ARG(!input_only || (dx && !drain_in), "eagcn_layer_backward: the input-only form needs dx and takes no edge reduction");
+    EAGCN_CHECK_ARG(b->T == 0 || ((dxout || rg) && (input_only || w->x || w->x_planes) && w->P && w->Y && w->rscale),
+                    "eagcn_layer_backward: null activation buffer");
+    if (!input_only)
+        for (int k = 0; k < p->K; ++k)
+            EAGCN_CHECK_ARG(g->dW[k] && g->dbias[k] && g->dgamma[k] && g->dbeta[k] && g->datt_w[k] && g->dself_r[k],
+                            "eagcn_layer_backward: view %d has a null gradient buffer", k);
     const LayerDims d = layer_dims(b, p);
     BwdScratch sc;
     const size_t need = carve_bwd(w->scratch, b, d, &sc);
@@ -1242,11 +1245,23 @@ int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p
     const ParamPtrs pp = param_ptrs(b, p);
     GradPtrs gp;
     memset(&gp, 0, sizeof(gp));
-    for (int k = 0; k < p->K; ++k) {
-        gp.dW[k] = g->dW[k]; gp.dbias[k] = g->dbias[k]; gp.dgamma[k] = g->dgamma[k]; gp.dbeta[k] = g->dbeta[k];
-        gp.datt_w[k] = g->datt_w[k]; gp.dself_r[k] = g->dself_r[k];
+    if (input_only) {
+        // (a training-mode BatchNorm finalize still writes d gamma / d beta / d bias / d ave.weight on its way: into the weight-gradient
+        //  slab area, which this form does not use; nothing reads them)
+        EAGCN_CHECK_ARG(d.wslab >= (size_t)3 * d.fp + EAGCN_MAX_VIEWS, "eagcn_layer_backward: no room for the discarded BatchNorm gradients");
+        for (int k = 0; k < p->K; ++k) {
+            gp.dgamma[k] = sc.dWcat + d.vc.off[k];
+            gp.dbeta[k] = sc.dWcat + d.fp + d.vc.off[k];
+            gp.dbias[k] = sc.dWcat + 2 * d.fp + d.vc.off[k];
+        }
+        gp.dave_w = p->structure == EAGCN_STRUCT_WEIGHTED ? sc.dWcat + 3 * d.fp : nullptr;
+    } else {
+        for (int k = 0; k < p->K; ++k) {
+            gp.dW[k] = g->dW[k]; gp.dbias[k] = g->dbias[k]; gp.dgamma[k] = g->dgamma[k]; gp.dbeta[k] = g->dbeta[k];
+            gp.datt_w[k] = g->datt_w[k]; gp.dself_r[k] = g->dself_r[k];
+        }
+        gp.dave_w = p->structure == EAGCN_STRUCT_WEIGHTED ? g->dave_w : nullptr;
     }
-    gp.dave_w = p->structure == EAGCN_STRUCT_WEIGHTED ? g->dave_w : nullptr;
     const ColMapD in = make_colmap(&p->in);
     if (w->packed) {          // parameters were re-laid by the forward call and kept
         Packed pk;
@@ -1285,7 +1300,7 @@ int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p
     if (drain_in && drain_in->eacc) ba.drain = *drain_in; else memset(&ba.drain, 0, sizeof(ba.drain));
     const int rows = b->T + ba.nvirt;
     const int gxb = std::max(1, std::min(rows, d.gxb));
-    bool fused_bn_apply = false, fused_w_apply = false, w_rows = false;
+    bool fused_bn_apply = false, fused_w_apply = false, w_rows = false, fused_c_apply = false;
     // the LDS-staged aggregation (lagg.hip) runs this layer's transposed aggregation + edge gradients: decided ONCE, here, because the
     // BatchNorm backward below leaves its second pass to that kernel (the edge gradients must then leave through the shared accumulators)
     bool lagg_bwd = false;
@@ -1296,9 +1311,33 @@ int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p
         const bool wt0 = p->structure == EAGCN_STRUCT_WEIGHTED;
         const bool absorbs = lagg_fuses_bn() && (!bn_bwd_two_pass(wt0) || (wt0 && lagg_wfuse()));
         lagg_bwd = b->T > 0 && edge_atomic0 && !general0 && lagg_use(b, 1, absorbs);
+        // input-only: no edge gradients to route, and the staging absorbs the BatchNorm backward whatever the structure
+        if (input_only) lagg_bwd = b->T > 0 && lagg_use(b, 1, true);
     }
     const double M = (double)b->B * (double)b->N;
-    {
+    const bool eval_in = input_only && !p->training;
+    if (eval_in) {
+        // eval-mode BatchNorm backward of the input-only form: dY' = sc dH (the running statistics are constants: c1 = c2 = 0), no
+        // reduction and no finalize.  With the LDS-staged aggregation dH and dY' are formed in its staging from the upstream gradient
+        // (a per-molecule read-out gradient is written as rows first); otherwise the reduction kernel's APPLY pass forms dY' from zero means
+        const bool wt = p->structure == EAGCN_STRUCT_WEIGHTED, dg = ba.rg.dg != nullptr;
+        if (b->T > 0 && lagg_bwd) {
+            if (dg) {
+                rc = launch_readout_bwd_rows(b, ba.rg, d.ldo, sc.dY, s);
+                if (rc) return rc;
+                w_rows = true;
+            }
+            if (wt) fused_w_apply = true; else fused_c_apply = true;
+        } else if (b->T > 0) {
+            rc = zero_fill(sc.cc, (size_t)2 * d.fp * sizeof(float), s);
+            if (rc) return rc;
+            ba.cc = sc.cc;
+            launch_bn_bwd_pass(true, wt, dg, false, dim3(std::max(1, std::min(b->T, d.gxb)), cdiv(d.fp, 1024)), ba, s);
+            EAGCN_LAUNCH_CHECK();
+        }
+        // (the head's backward sums are left zero for a later backward call: the finalize that clears them on the way did not run)
+        if (zero_after && zero_after->nd) { rc = zero_fill(zero_after->d, (size_t)zero_after->nd * sizeof(double), s); if (rc) return rc; }
+    } else {
         ProfScope ps(PROF_BN, s);
         const int ny = cdiv(d.fp, 1024);
         {
@@ -1384,11 +1423,11 @@ int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p
         }
         if (use_bx) {
             a.planes = BxOut{sc.dPp, pstride, d.np, b->T};
-            if (!w->x_planes) {
+            if (!w->x_planes && !input_only) {
                 rc = launch_bx3_split(w->x, b->T, b->meta + EAGCN_META_T, d.ld_in, sc.xp, xstride, b->T, d.np, s);
                 if (rc) return rc;
             }
-        } else if (!w->x) {
+        } else if (!w->x && !input_only) {
             set_error("eagcn_layer_backward: the input exists as plane images only and the plane products do not apply");
             return EAGCN_ERR_ARG;
         }
@@ -1401,6 +1440,30 @@ int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p
         if (edge_atomic && !general_rel) { e.datt = sc.eacc; e.atomic = 1; }
         static const bool colaunch = [] { const char* v = getenv("EAGCN_NO_COLAUNCH"); return !(v && v[0] == '1'); }();
         nedge = e.atomic ? -EDGE_COPIES : edge_grid_x(b);
+        if (input_only) {
+            // ---- d(layer input) alone: the transposed aggregation without edge gradients, then dX = dP . Wcat^T as ONE product
+            if (lagg_bwd) {
+                if (fused_bn_apply || fused_w_apply || fused_c_apply) { a.bn_tab = w->bn; a.bn_cc = eval_in ? nullptr : sc.cc; a.bn_fp = d.fp; }
+                if (fused_w_apply || fused_c_apply) {
+                    a.src = (ba.rg.dg || w_rows) ? sc.dY : dxout; a.lds = d.ldo;
+                    a.w_aw = sc.colp + (size_t)CP_AVEW * d.fp;
+                    a.w_rowm = fused_c_apply;
+                    a.w_drop = ba.do_drop; a.w_thr = ba.thr; a.w_inv_keep = ba.inv_keep; a.w_seed = ba.seed; a.w_seed_dev = ba.seed_dev;
+                }
+                rc = launch_lagg_bwd(a, e, s, false);
+            } else {
+                rc = launch_agg(a, true, s);                                     // (agg.hip: molecules of more than 256 atoms, code books)
+            }
+            if (rc) return rc;
+            if (use_bx) {
+                rc = launch_bx3(bx, nullptr, d.np, s, gemm_work, PROF_GEMM, bx3_pick_wide(bx, nullptr, b->t_hint));
+            } else {
+                GemmDesc gx{0, 1, b->T, d.ld_in, d.fp, sc.dP, d.fp, sc.Wcat, d.fp, dx, d.ld_in, 1, 0, gemm_work};
+                gx.M_dev = b->meta + EAGCN_META_T;
+                rc = launch_gemm(gx, s);
+            }
+            return rc;
+        }
         if (lagg_bwd && e.atomic) {                                              // transposed aggregation + edge gradients from the same LDS gathers
             if (fused_bn_apply || fused_w_apply) { a.bn_tab = w->bn; a.bn_cc = sc.cc; a.bn_fp = d.fp; }
             if (fused_w_apply) {
@@ -1460,6 +1523,7 @@ int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p
             if (dx) { rc = launch_gemm(gx, s); if (rc) return rc; }
         }
     }
+    if (b->T == 0 && input_only) return EAGCN_OK;          // (no packed row: d(layer input) has no entry)
     if (b->T == 0) {
         // a batch without a single bond has no packed row: no product ran, the weight gradients are exactly zero (the edge
         // partials below are summed over zero workgroups; the BatchNorm gradients came from the row-less reduction above)

@@ -24,6 +24,7 @@ import os
 import torch
 
 from . import _lib as L
+from . import ops
 from .ops import _index_stream, _ptr, _stream
 
 _RING = 4
@@ -238,6 +239,7 @@ class GraphRunner:
         self._xout_views = [sv[xo.value:xo.value + 4 * T * ld.value].view(torch.float32).view(T, ld.value) for sv in self.saved]
         self._pad_views = [sv[po.value:po.value + 4 * ld.value].view(torch.float32) for sv in self.saved]
         self.ptrs = [t.data_ptr() for t in plan._ptr_tensors]
+        self._attr = None              # static buffers + captured graphs of atom attributions (attributions(); built on first use)
 
     def nbytes(self):
         """Device memory this runner holds (two index slots, two saved-activation blocks, scratch, gradients)."""
@@ -252,6 +254,7 @@ class GraphRunner:
         self.graphs = [[None, None, None], [None, None, None]]
         self.saved, self.scratch, self.slots, self.index = [], None, [], None
         self._xout_views, self._pad_views = [], []
+        self._attr = None
 
     def materializer(self):
         """Callable that builds the current slot's top-layer output matrix (atom representations) when the forward skipped it
@@ -563,6 +566,62 @@ class GraphRunner:
             self.fwd_done = torch.cuda.Event()
             self.fwd_done.record(main)
         return self.generation
+
+    def attributions(self, adj, rels, afm, size, dout, steps, baseline, bonds=None):
+        """Atom attributions of one eval batch (EAGCN.atom_attributions, graph mode): the whole m-point loop of
+        ops.attribution_launches -- pack, forward, input-only backward, accumulate, then finalize -- as ONE captured graph per
+        (slot, steps, baseline or not), over static buffers of its own (a scratch block sized for the input backward; the forward
+        graphs of the runner keep theirs).  The first call of a key runs the sequence eagerly (the capture warm-up).  Returns fresh
+        (score [B, N], attr [B, N, F])."""
+        if self.training:
+            raise L.EagcnHipError('graph-mode attributions run on the eval runner')
+        lib = L.load()
+        if self._attr is None:
+            m = self.cms[0]
+            B, F = self.key[0], int(afm.shape[2])
+            a = ops.attribution_buffers(self.index.ref(), m, B, self.key[1], F, self.device)
+            a.update(afm=torch.zeros((B, self.key[1], F), dtype=torch.float32, device=self.device), base=torch.zeros_like(afm),
+                     dout=torch.zeros((B, m.head.nclass), dtype=torch.float32, device=self.device), graphs={})
+            self._attr = a
+        a = self._attr
+        if afm.shape != a['afm'].shape:
+            raise L.EagcnHipError('attributions: afms %s, the runner holds %s' % (tuple(afm.shape), tuple(a['afm'].shape)))
+        self._prepare(adj, rels, afm, size, 0, False, bonds)         # index + seeds + sizes into the slot; main stream in order
+        cur = self.cur
+        a['afm'].copy_(afm)
+        a['dout'].copy_(dout)
+        if steps and baseline is not None:
+            a['base'].copy_(baseline)
+        # the first forward consumes the slot's ready flag and counts a start like every forward; the others carry no hand-off
+        m_first = L.Model.from_buffer_copy(self.cms[cur])
+        m_rest = L.Model.from_buffer_copy(self.cms[cur])
+        m_rest.wait_flag = m_rest.start_signal = m_rest.fwd_signal = None
+        size_ptr = _ptr(self.size_static[cur]) if self.plan.molfp else C.c_void_p(0)
+        key = (cur, int(steps), steps and baseline is not None)
+
+        def run():
+            ops.attribution_launches(self.index.ref(), m_first, m_rest, size_ptr, a['saved'], a['scratch'], a['out'], a['graph_rep'],
+                                     a['afm'], a['base'] if key[2] else None, a['dout'], a['acc'], a['attr'], a['score'], steps)
+        try:
+            g = a['graphs'].get(key)
+            if g is None:
+                self._set_row_hint()
+                run()                                                 # eager: the result of this call, and the capture warm-up
+                a['models'] = a.get('models', []) + [m_first, m_rest]  # (the captured launches read these structs' values at capture)
+                lib.eagcn_prof_enable(0)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode='thread_local'):
+                    run()
+                a['graphs'][key] = g
+            else:
+                g.replay()
+        except BaseException:
+            self._reset_ready()
+            raise
+        if self.side_placed:
+            self.fwd_issued += 1
+        self.starts_issued += 1
+        return a['score'].clone(), a['attr'].clone()
 
     def outputs(self):
         """(out, graph_representation) of the last forward.  By default fresh tensors, as the reference returns

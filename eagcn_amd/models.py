@@ -475,6 +475,89 @@ class EAGCN(nn.Module):
                 atom_representations = atom_representations.cpu()
         return out, atom_representations, graph_representation
 
+    def atom_attributions(self, adjs, afms, *rels, size, target, steps=0, baseline=None, bonds=None):
+        """Per-atom attributions of a prediction -> (score [B, N], attr [B, N, n_afeat]), score = attr summed over the features.
+
+        ``target``: a task index, or a [B, nclass] weight tensor; the attributed scalar is sum(out * target).  ``steps = 0``:
+        gradient x input, attr = x * d target / d x.  ``steps = m >= 1``: integrated gradients against ``baseline`` (default
+        zeros) by the midpoint rule, alpha_s = (s + 1/2) / m, w_s = 1 / m (include/eagcn_hip.h, "attribution").  ``bonds``: a
+        compact batch (``adjs`` / ``rels`` are then ignored), as ``forward_compact``.  Eval mode only; running statistics and the
+        parameters' ``.grad`` are not touched.  With ``graph=True`` the whole m-point loop is one captured HIP graph per
+        (B, N, steps) (released by ``release_graphs``).  GAT and Diff_Pooling models run the same computation through
+        ``forward_composed`` and autograd.  Rows that are not stored (padding, trailing bond-less atoms) are 0 on the engine."""
+        if self.training:
+            raise ops.L.EagcnHipError('atom_attributions needs model.eval(): in training mode the BatchNorm batch statistics couple '
+                                      'the molecules of a batch and a per-molecule attribution is not defined')
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError('steps must be >= 0')
+        afms = ops._need_cuda_f32(afms, 'afms').detach()
+        B = int(afms.shape[0])
+        nclass = self.den3.weight.shape[1]
+        if isinstance(target, torch.Tensor):
+            dout = target.to(device=afms.device, dtype=torch.float32).reshape(B, nclass).contiguous()
+        else:
+            t = int(target)
+            if not 0 <= t < nclass:
+                raise ValueError('target task %d out of range (nclass %d)' % (t, nclass))
+            dout = torch.zeros((B, nclass), dtype=torch.float32, device=afms.device)
+            dout[:, t] = 1.0
+        if baseline is not None:
+            baseline = ops._need_cuda_f32(baseline, 'baseline').detach()
+            if baseline.shape != afms.shape:
+                raise ops.L.EagcnHipError('baseline is %s, afms %s' % (tuple(baseline.shape), tuple(afms.shape)))
+        if bonds is None and self.relations == 'general' and self.structure in ('Concate', 'Weighted_sum'):
+            from .collate import bonds_from_dense
+            bonds = bonds_from_dense(ops._need_cuda_f32(adjs, 'adjs'), rels)
+        if self.structure == 'GAT' or self.molfp_mode == 'pool':
+            return self._attributions_composed(adjs, afms, rels, size, dout, steps, baseline, bonds)
+        if self.graph:
+            if bonds is not None and self.structure == 'GCN':
+                bonds = bonds.first_view()
+            runner, adjs_, rels_, afms_, size_, _, btuple = self._graph_runner(adjs, afms, rels[:1] if self.structure == 'GCN' else rels,
+                                                                              size, bonds)
+            return runner.attributions(adjs_, rels_, afms_, size_, dout, steps, baseline, btuple)
+        if bonds is not None:
+            if self.structure == 'GCN':
+                bonds = bonds.first_view()
+            self._check_channels(bonds.channels, bonds.rel_vectors)
+            index = ops.BatchIndex.from_bonds(bonds.B, bonds.N, bonds.channels, *bonds.checked(), rel_vectors=bonds.rel_vectors)
+        else:
+            if self.structure == 'GCN':
+                rels = rels[:1]
+            self._check_channels([int(r.shape[1]) for r in rels])
+            index = ops.BatchIndex(adjs, rels, structure={'Concate': 0, 'Weighted_sum': 1}.get(self.structure, -1))
+        plan = self.plan()
+        m = ops.L.Model.from_buffer_copy(plan.cmodel(False, 0, self.dropout))
+        m.input_packed = 1
+        if afms.shape[:2] != (index.B, index.N):
+            raise ops.L.EagcnHipError('afms is %s for a batch of B=%d N=%d' % (tuple(afms.shape), index.B, index.N))
+        if plan.molfp:
+            size = size.to(device=afms.device, dtype=torch.int64).contiguous()
+        bufs = ops.attribution_buffers(index.ref(), m, index.B, index.N, int(afms.shape[2]), afms.device)
+        ops.attribution_launches(index.ref(), m, m, ops._ptr(size) if plan.molfp else ops.C.c_void_p(0), bufs['saved'], bufs['scratch'],
+                                 bufs['out'], bufs['graph_rep'], afms, baseline, dout, bufs['acc'], bufs['attr'], bufs['score'], steps)
+        return bufs['score'], bufs['attr']
+
+    def _attributions_composed(self, adjs, afms, rels, size, dout, steps, baseline, bonds):
+        """atom_attributions of the models without an engine path (GAT, Diff_Pooling): the same quadrature through
+        forward_composed (or the compact entry) and autograd -- eager, d / d afms only."""
+        base = baseline if (steps and baseline is not None) else torch.zeros_like(afms)
+        x = afms
+        pts = [((s + 0.5) / steps, 1.0 / steps) for s in range(steps)] if steps else [(1.0, 1.0)]
+        acc = torch.zeros_like(x)
+        for alpha, w in pts:
+            xa = (base + alpha * (x - base)).requires_grad_(True)
+            with torch.enable_grad():
+                if bonds is not None:
+                    out = self.forward_compact(bonds, xa, size)[0]
+                else:
+                    out = self.forward_composed(adjs, xa, *rels, size)[0]
+                g, = torch.autograd.grad((out * dout).sum(), xa)
+            acc.add_(g, alpha=w)
+        attr = (x - base) * acc
+        return attr.sum(-1), attr
+
     def release_graphs(self):
         """Destroy every captured HIP graph and static buffer of this model NOW (they are rebuilt by the next forward).  Orderly
         shutdown of a data-parallel run: the step graphs hold RCCL kernels and must be gone before the process group."""

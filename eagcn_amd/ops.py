@@ -880,15 +880,15 @@ class ModelPlan:
 
 class _ModelFn(torch.autograd.Function):
     """(afm, every hot parameter) -> (out, graph_representation): one call into
-    eagcn_model_forward, one into eagcn_model_backward."""
+    eagcn_model_forward, one into eagcn_model_backward -- or, when afm requires a gradient, into eagcn_model_backward_input
+    (the same parameter gradients plus d/d afm; input-only when no parameter needs a gradient)."""
 
     @staticmethod
     def forward(ctx, plan, index, holder, training, seed, dropout, size, afm, trigger, *params):
         lib = L.load()
-        if ctx.needs_input_grad[7]:
-            raise L.EagcnHipError('the model-level engine does not produce d/d(afms) (the reference training loop never '
-                                  'asks for it); use EAGCN.forward_composed, whose layer-level ops return it')
+        ctx.want_afm = bool(ctx.needs_input_grad[7])
         afm = _need_cuda_f32(afm, 'afms')
+        ctx.afm_shape = tuple(afm.shape)
         ctx.direct = trigger is not None
         if ctx.direct:
             params = plan.params
@@ -902,7 +902,8 @@ class _ModelFn(torch.autograd.Function):
         if plan.molfp:
             size = size.to(device=dev, dtype=torch.int64).contiguous()
         sbytes = lib.eagcn_model_saved_bytes(index.ref(), C.byref(m))
-        wbytes = lib.eagcn_model_scratch_bytes(index.ref(), C.byref(m))
+        # (d/d afm: the backward's larger scratch already here -- the backward finds the block the forward left, see _scratch)
+        wbytes = (lib.eagcn_model_input_scratch_bytes if ctx.want_afm else lib.eagcn_model_scratch_bytes)(index.ref(), C.byref(m))
         saved = torch.empty(sbytes, dtype=torch.uint8, device=dev)
         scratch = _scratch(dev, wbytes)
         out = torch.empty((index.B, m.head.nclass), dtype=torch.float32, device=dev)
@@ -940,6 +941,21 @@ class _ModelFn(torch.autograd.Function):
         dev = saved.device
         dout = dout.contiguous()
         dgr = dgraph_rep.contiguous() if dgraph_rep is not None else None
+        if ctx.direct:
+            want_params = any(p.requires_grad for p in plan.params)
+        else:
+            want_params = any(ctx.needs_input_grad[9:])     # (inputs: plan .. size, afm = 7, trigger = 8, params from 9)
+        if ctx.want_afm and not want_params:
+            # d/d afm alone (attribution through autograd): the input-only backward forms no parameter gradient
+            dafm = torch.empty(ctx.afm_shape, dtype=torch.float32, device=dev)
+            scratch = _scratch(dev, lib.eagcn_model_input_scratch_bytes(index.ref(), C.byref(m)))
+            L.check(lib.eagcn_model_backward_input(index.ref(), C.byref(m), _ptr(ctx.size) if plan.molfp else C.c_void_p(0),
+                                                   _ptr(saved), saved.numel(), _ptr(scratch), scratch.numel(), _ptr(dout), _ptr(dgr),
+                                                   None, None, _ptr(dafm), _stream()), 'eagcn_model_backward_input')
+            ctx.saved_blob = None
+            if ctx.direct:
+                return (None,) * 7 + (dafm, None)
+            return (None,) * 7 + (dafm,) + (None,) * (1 + len(plan.params))
         flat = torch.zeros(plan.offsets[-1], dtype=torch.float32, device=dev)
         base = flat.data_ptr()
 
@@ -958,10 +974,18 @@ class _ModelFn(torch.autograd.Function):
         for j, name in enumerate(('d_den1_w', 'd_den2_w', 'd_den3_w', 'd_gbn_w', 'd_gbn_b', 'd_bn1_w', 'd_bn1_b',
                                   'd_bn2_w', 'd_bn2_b')):
             setattr(hg, name, gptr(hs + j))
-        scratch = _scratch(dev, lib.eagcn_model_scratch_bytes(index.ref(), C.byref(m)))
-        L.check(lib.eagcn_model_backward(index.ref(), C.byref(m), _ptr(ctx.size) if plan.molfp else C.c_void_p(0),
-                                         _ptr(saved), saved.numel(), _ptr(scratch), scratch.numel(), _ptr(dout),
-                                         _ptr(dgr), lg, C.byref(hg), _stream()), 'eagcn_model_backward')
+        dafm = None
+        if ctx.want_afm:                               # the same backward, layer 0 also forming d(input)
+            dafm = torch.empty(ctx.afm_shape, dtype=torch.float32, device=dev)
+            scratch = _scratch(dev, lib.eagcn_model_input_scratch_bytes(index.ref(), C.byref(m)))
+            L.check(lib.eagcn_model_backward_input(index.ref(), C.byref(m), _ptr(ctx.size) if plan.molfp else C.c_void_p(0),
+                                                   _ptr(saved), saved.numel(), _ptr(scratch), scratch.numel(), _ptr(dout), _ptr(dgr),
+                                                   lg, C.byref(hg), _ptr(dafm), _stream()), 'eagcn_model_backward_input')
+        else:
+            scratch = _scratch(dev, lib.eagcn_model_scratch_bytes(index.ref(), C.byref(m)))
+            L.check(lib.eagcn_model_backward(index.ref(), C.byref(m), _ptr(ctx.size) if plan.molfp else C.c_void_p(0),
+                                             _ptr(saved), saved.numel(), _ptr(scratch), scratch.numel(), _ptr(dout),
+                                             _ptr(dgr), lg, C.byref(hg), _stream()), 'eagcn_model_backward')
         ctx.saved_blob = None
         grads = plan.grad_views(flat)
         if ctx.direct:
@@ -975,8 +999,44 @@ class _ModelFn(torch.autograd.Function):
                 else:
                     p.grad.add_(g)
             plan.flat_grad = flat
-            return (None,) * 10
-        return (None, None, None, None, None, None, None, None, None, *grads)
+            return (None,) * 7 + (dafm, None)
+        return (None, None, None, None, None, None, None, dafm, None, *grads)
+
+
+def attribution_launches(index_ref, m_first, m_rest, size_ptr, saved, scratch, out, graph_rep, afm, baseline, dout, acc, attr, score,
+                         steps):
+    """The launch sequence of one attribution (include/eagcn_hip.h, "attribution"): per quadrature point the packed input
+    x' + alpha_s (x - x'), the forward (input_packed = 1) and the input-only backward accumulating w_s dX0 in packed rows; then ONE
+    finalize.  steps = 0: gradient x input (one point, alpha = 1, no baseline).  Issues launches only (capturable); `m_first` is
+    the model struct of the first forward (it may carry stream hand-offs), `m_rest` that of the others."""
+    lib = L.load()
+    npts = max(int(steps), 1)
+    base = _ptr(baseline) if (steps and baseline is not None) else C.c_void_p(0)
+    sb, wb = saved.numel(), scratch.numel()
+    for s in range(npts):
+        alpha = lib.eagcn_attr_alpha(s, steps) if steps else 1.0
+        w = lib.eagcn_attr_weight(steps) if steps else 1.0
+        m = m_first if s == 0 else m_rest
+        L.check(lib.eagcn_attr_pack_input(index_ref, C.byref(m), _ptr(afm), base, alpha, _ptr(saved), sb, _stream()),
+                'eagcn_attr_pack_input')
+        L.check(lib.eagcn_model_forward(index_ref, C.byref(m), C.c_void_p(0), size_ptr, _ptr(saved), sb, _ptr(scratch), wb,
+                                        _ptr(out), _ptr(graph_rep), _stream()), 'eagcn_model_forward')
+        L.check(lib.eagcn_attr_step(index_ref, C.byref(m), size_ptr, _ptr(saved), sb, _ptr(scratch), wb, _ptr(dout), C.c_void_p(0),
+                                    w, 1 if s == 0 else 0, _ptr(acc), _stream()), 'eagcn_attr_step')
+    L.check(lib.eagcn_attr_finalize(index_ref, C.byref(m_rest), _ptr(afm), base, _ptr(acc), _ptr(attr), _ptr(score), _stream()),
+            'eagcn_attr_finalize')
+
+
+def attribution_buffers(index_ref, m, B, Nin, F, device):
+    """Device buffers of attribution_launches for one batch shape: saved / scratch blocks, out / graph_rep, the packed accumulator,
+    attr [B, Nin, F], score [B, Nin]."""
+    lib = L.load()
+    f32 = dict(dtype=torch.float32, device=device)
+    return dict(saved=torch.empty(lib.eagcn_model_saved_bytes(index_ref, C.byref(m)), dtype=torch.uint8, device=device),
+                scratch=torch.empty(lib.eagcn_model_input_scratch_bytes(index_ref, C.byref(m)), dtype=torch.uint8, device=device),
+                out=torch.empty((B, m.head.nclass), **f32), graph_rep=torch.empty((B, m.head.n_den2), **f32),
+                acc=torch.empty(int(lib.eagcn_attr_acc_elems(index_ref, C.byref(m))), **f32),
+                attr=torch.empty((B, Nin, F), **f32), score=torch.empty((B, Nin), **f32))
 
 
 def model_forward(plan, index, holder, training, seed, dropout, size, afm, direct=False):

@@ -28,6 +28,8 @@
  *   eagcn_model_forward / eagcn_model_backward
  *                        <- EAGCN.forward models.py:96-121 end to end (layers, read-out, Graph_BN,
  *                           den1/bn_den1/relu/dropout/den2/bn_den2/relu/den3) and its autograd backward
+ *   eagcn_model_backward_input / eagcn_attr_*
+ *                        <- afm.requires_grad_() (models.py:96) and autograd to the atom features; integrated gradients
  *
  * Conventions: all pointers are device pointers unless named host_*; tensors are fp32,
  * contiguous, row-major; `stream` is a hipStream_t passed as void*; functions return 0 on
@@ -432,6 +434,44 @@ int eagcn_model_backward_range(const eagcn_batch* b, const eagcn_model* m, const
                                size_t saved_bytes, void* scratch, size_t scratch_bytes, const float* dout,
                                const float* dgraph_rep, const eagcn_layer_grads* lg, const eagcn_head_grads* hg,
                                int with_head, int layer_hi, int layer_lo, void* stream);
+
+/* ---- d / d afm: the gradient of a prediction with respect to the atom features ("which atoms drive this prediction") ----------------
+ * d(out.dout + graph_rep.dgraph_rep) / d afm, dense [B][N][n_afeat] (the row stride eagcn_model_pack_input reads): every entry written
+ * (rows that are not stored are 0).  dgraph_rep may be NULL.
+ *   lg, hg non-NULL: the same parameter gradients as eagcn_model_backward, plus dafm.
+ *   lg == NULL && hg == NULL: INPUT-ONLY backward: no parameter gradient is formed.  Per hidden layer only the transposed aggregation
+ *     (no edge gradients) and dX = dP.Wcat^T run; in eval mode (m->training == 0) no BatchNorm reduction either (the eval BatchNorm
+ *     backward is the per-column scale gamma rsqrt(rv + eps) with the relu / view-merge mask, applied where the aggregation stages its
+ *     rows).  The head's backward kernels run with their weight gradients written into `scratch`.  Training mode keeps the
+ *     BatchNorm reductions (the mean-removal terms need them) and still skips every weight and edge gradient.
+ * scratch_bytes >= eagcn_model_input_scratch_bytes (the model scratch plus layer 0's packed d(input) and the discarded head gradients).
+ * Rejected before any HIP call: dafm NULL; exactly one of lg / hg NULL; a structure or read-out the engine does not run (GAT, pool). */
+size_t eagcn_model_input_scratch_bytes(const eagcn_batch* b, const eagcn_model* m);
+int eagcn_model_backward_input(const eagcn_batch* b, const eagcn_model* m, const int64_t* size, void* saved,
+                               size_t saved_bytes, void* scratch, size_t scratch_bytes, const float* dout,
+                               const float* dgraph_rep, const eagcn_layer_grads* lg, const eagcn_head_grads* hg,
+                               float* dafm, void* stream);
+
+/* ---- attribution: integrated gradients (csrc/attr.hip) ------------------------------------------------------------------------------
+ * attr = (x - x') . integral_0^1 d target / d x (x' + a (x - x')) da  by the MIDPOINT rule over m points:
+ *     alpha_s = (s + 1/2) / m,   w_s = 1 / m,   s = 0 .. m-1          (eagcn_attr_alpha / eagcn_attr_weight return them)
+ * One point: eagcn_attr_pack_input(alpha_s) -> eagcn_model_forward with m->input_packed = 1 -> eagcn_attr_step(w_s, first = s == 0);
+ * then ONE eagcn_attr_finalize.  m = 1 with alpha = 1 and no baseline is gradient x input.  Every call is capturable (no host sync). */
+float eagcn_attr_alpha(int step, int steps);
+float eagcn_attr_weight(int steps);
+/* floats of the packed accumulator [T][ld] (ld: the packed width of layer 0's input layout) */
+size_t eagcn_attr_acc_elems(const eagcn_batch* b, const eagcn_model* m);
+/* packs baseline + alpha (afm - baseline) into the input slot of `saved` (what eagcn_model_pack_input fills); baseline NULL = 0 */
+int eagcn_attr_pack_input(const eagcn_batch* b, const eagcn_model* m, const float* afm, const float* baseline, float alpha,
+                          void* saved, size_t saved_bytes, void* stream);
+/* the input-only backward of eagcn_model_backward_input behind a forward, then acc = weight dX0 (first != 0) or acc += weight dX0, in
+ * packed rows (the dense gradient of a point is not formed).  scratch_bytes >= eagcn_model_input_scratch_bytes */
+int eagcn_attr_step(const eagcn_batch* b, const eagcn_model* m, const int64_t* size, void* saved, size_t saved_bytes,
+                    void* scratch, size_t scratch_bytes, const float* dout, const float* dgraph_rep, float weight, int first,
+                    float* acc, void* stream);
+/* attr[B][N][n_afeat] = (afm - baseline) * acc (0 at rows that are not stored), score[B][N] = sum over the features: one launch */
+int eagcn_attr_finalize(const eagcn_batch* b, const eagcn_model* m, const float* afm, const float* baseline, const float* acc,
+                        float* attr, float* score, void* stream);
 
 /* ---- a training step's forward + loss + HEAD backward as one call (reference train.py:317-331 in front of models.py:112-120 and
  * their autograd): the model forward as eagcn_model_forward, then the loss on `out` and the backward of den3 / bn_den2 / den2 /
