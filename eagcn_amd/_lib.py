@@ -34,6 +34,48 @@ class Batch(C.Structure):
                 ('build_lists', C.c_int32), ('t_hint', C.c_int32), ('blk', _fp)]
 
 
+def _slices(fields):
+    out, o = {}, 0
+    for name, n in fields:
+        out[name] = slice(o, o + n)
+        o += n
+    out['all'] = slice(0, o)
+    return out
+
+
+def index_layout(B, N, T=0, n_tiles=0):
+    """The two int32 buffers of a batch index as {field: slice in words} (plus 'all'), the ONE place their layout is written:
+    blob [deg_bn B*N | nat B | row0 B+1 | tile0 B+1 | meta | ecnt B | edge0 B+1 | one spare word], known from the batch shape alone, and
+    rows [row_info 4T | tile_info 4*n_tiles (both 16-byte aligned) | row_mol | row_loc | row_deg | row_m (f32) | tile_mol],
+    known once the row capacity is (the eager index sizes it after its host read)."""
+    blob = _slices((('deg_bn', B * N), ('nat', B), ('row0', B + 1), ('tile0', B + 1), ('meta', META_WORDS), ('ecnt', B),
+                    ('edge0', B + 1), ('spare', 1)))
+    rows = _slices((('row_info', 4 * T), ('tile_info', 4 * n_tiles), ('row_mol', T), ('row_loc', T), ('row_deg', T), ('row_m', T),
+                    ('tile_mol', n_tiles)))
+    return blob, rows
+
+
+def new_batch(B, N, channels):
+    c = Batch()
+    c.B, c.N, c.K, c.ldc = B, N, len(channels), pad16(N)
+    for k, ch in enumerate(channels):
+        c.channels[k] = int(ch)
+    return c
+
+
+def point_batch(c, blob_ptr, rows_ptr=None, ptrs=None, edges=None, E=None):
+    """Point a Batch (B, N set; T, n_tiles too when `rows_ptr` is given) at its index buffers, laid out by index_layout:
+    `blob_ptr` / `rows_ptr` device addresses, `ptrs` / `edges` / `E` the bond-list buffers of set_bond_lists."""
+    blob, rows = index_layout(c.B, c.N, c.T, c.n_tiles)
+    for name in ('deg_bn', 'nat', 'row0', 'tile0', 'meta', 'ecnt', 'edge0'):
+        setattr(c, name, blob_ptr + 4 * blob[name].start)
+    if rows_ptr is not None:
+        for name in ('row_info', 'tile_info', 'row_mol', 'row_loc', 'row_deg', 'row_m', 'tile_mol'):
+            setattr(c, name, rows_ptr + 4 * rows[name].start)
+    if ptrs is not None:
+        set_bond_lists(c, c.ecnt, ptrs, edges, E)
+
+
 def bond_ptrs_len(T, B):
     return 4 * T + 4 * B + 8 * (B + 1) + 8
 
@@ -53,6 +95,43 @@ def set_bond_lists(c, small_ptr, ptrs, edges, E):
     code = eb + 8 * E
     code += (-code) % 8
     c.ecode, c.tcode = code, code + 8 * E
+
+
+def index_error(meta, row_cap=None, edge_cap=None, compact=False):
+    """What the validity words of an index build (`meta`: the META_WORDS host values) say against the batch: None, or the
+    message every path raises EagcnHipError with.  `compact`: the batch came as a bond list (eagcn_index_from_bonds).  The
+    overflow words are read against the capacities given (the eager index builds without any and passes none)."""
+    if meta[META_BAD_ADJ] and compact:
+        return '%d bonds are out of range or listed twice' % meta[META_BAD_ADJ]
+    if meta[META_BAD_ADJ]:
+        return ('adjs holds %d entries outside {0,1}: the hot path requires a 0/1 adjacency (reference neural_fp.py:85,109-110)'
+                % meta[META_BAD_ADJ])
+    if meta[META_BAD_REL]:
+        return ('%d bonded (i,j,view) positions are not one-hot over the relation channels (reference neural_fp.py:111-120); '
+                'build the model with relations=\'general\' for relation tensors with arbitrary channel values (layers.py:82)'
+                % meta[META_BAD_REL])
+    if row_cap is not None and meta[META_OVERFLOW]:
+        return ('%d packed rows, more than row_cap=%d (the batch is indexed as an empty batch; no memory is overwritten)'
+                % (meta[META_OVERFLOW], row_cap))
+    if edge_cap is not None and meta[META_EDGE_OVERFLOW]:
+        return ('%d directed bonds, more than edge_cap=%d (the batch is indexed as an empty batch; no memory is overwritten)'
+                % (meta[META_EDGE_OVERFLOW], edge_cap))
+    return None
+
+
+def dropout_seeds(seed, n_layers=4):
+    """Per-layer dropout seeds and the head's from one step seed.  Every path derives them here, so that the graph runners and
+    the eager engine draw the same masks for the same seed."""
+    seed = int(seed)
+    return [(seed + 7919 * (l + 1)) & (2 ** 63 - 1) for l in range(n_layers)], (seed + 0x51ED27) & (2 ** 63 - 1)
+
+
+STRUCTURES = {'Concate': 0, 'Weighted_sum': 1}         # = STRUCT_CONCATE, STRUCT_WEIGHTED
+
+
+def structure_code(name):
+    """EAGCN_STRUCT_* of a multi-view layer structure; -1 for the baselines (GCN, GAT), which have none."""
+    return STRUCTURES.get(name, -1)
 
 
 class GatParams(C.Structure):

@@ -110,35 +110,25 @@ class StaticIndex:
         K = len(channels)
         self.device, self.B, self.N, self.K = device, B, N, K
         self.channels = list(channels)
-        self.ldc = (N + 15) // 16 * 16
         self.T = int(row_cap)
         self.n_tiles = B * ((N + 15) // 16)
         self.n_max = N
+        c = L.new_batch(B, N, self.channels)
+        c.T, c.n_max, c.n_tiles = self.T, N, self.n_tiles
+        self.ldc = c.ldc
+        blob_lay, rows_lay = L.index_layout(B, N, self.T, self.n_tiles)
         i32 = dict(dtype=torch.int32, device=device)
         self.code = torch.empty((K, B, N, self.ldc), dtype=torch.uint8, device=device)
-        blob = torch.zeros(B * N + 3 * B + 2 + L.META_WORDS + 2 * B + 2, **i32)
-        rows = torch.zeros(8 * self.T + 5 * self.n_tiles, **i32)
+        blob = torch.zeros(blob_lay['all'].stop, **i32)
+        rows = torch.zeros(rows_lay['all'].stop, **i32)
         # bond lists (GAT layers, csrc/gat.hip): capacity in directed bonds; a molecular graph has 2-2.5 per atom
         self.E = int(edge_cap) if edge_cap else min(self.T * N, max(8 * self.T, 1024))
         self._ptrs = torch.zeros(L.bond_ptrs_len(self.T, B), **i32)
         self._edges = torch.zeros(6 * self.E + 2, **i32)       # nbr | tnbr | ecode (u64) | tcode (u64)
         self._blob, self._rows = blob, rows
-        o = B * N
-        self.nat = blob[o:o + B]
-        c = L.Batch()
-        c.B, c.N, c.K, c.ldc = B, N, K, self.ldc
-        c.T, c.n_max, c.n_tiles = self.T, N, self.n_tiles
-        for k in range(K):
-            c.channels[k] = self.channels[k]
-        base = blob.data_ptr()
-        c.code, c.deg_bn, c.nat = self.code.data_ptr(), base, base + 4 * B * N
-        c.row0, c.tile0 = base + 4 * (B * N + B), base + 4 * (B * N + 2 * B + 1)
-        c.meta = base + 4 * (B * N + 3 * B + 2)
-        rb, T = rows.data_ptr(), self.T
-        c.row_info, c.tile_info = rb, rb + 16 * T
-        ob = rb + 16 * T + 16 * self.n_tiles
-        c.row_mol, c.row_loc, c.row_deg, c.row_m, c.tile_mol = ob, ob + 4 * T, ob + 8 * T, ob + 12 * T, ob + 16 * T
-        L.set_bond_lists(c, base + 4 * (B * N + 3 * B + 2 + L.META_WORDS), self._ptrs, self._edges, self.E)
+        self.nat = blob[blob_lay['nat']]
+        c.code = self.code.data_ptr()
+        L.point_batch(c, blob.data_ptr(), rows.data_ptr(), self._ptrs, self._edges, self.E)
         # bond lists + row blocks: built when the library takes a bond-list form of the aggregation for this shape and layer structure
         # (csrc/lagg.hip); the GAT runner sets the flag itself
         self.bond_lists = bool(L.load().eagcn_agg_wants_bond_lists_for(B, N, int(structure)))
@@ -179,6 +169,7 @@ class GraphRunner:
         self.seeds_host = [torch.zeros(8, dtype=torch.int64).pin_memory() for _ in range(_RING)]
         self.meta_host = [torch.zeros(L.META_WORDS, dtype=torch.int32).pin_memory() for _ in range(_RING)]
         self.meta_event = [None] * _RING
+        self.meta_compact = [False] * _RING    # per ring slot: the batch came as a bond list (the wording of its validity report)
         self.step = 0
         self.cur = 0
         self.t_hint = None             # packed rows of the first batch (_set_row_hint): the size hint of every captured launch
@@ -232,7 +223,7 @@ class GraphRunner:
         n = plan.offsets[-1]
         self.flat_acc = torch.zeros(n, **f32)               # the captured backward writes here; p.grad are views of it
         self.acc_views = plan.grad_views(self.flat_acc)
-        self._grads_struct()
+        self.lg, self.hg = plan.grad_structs(self.flat_acc)
         xo, po, ld = C.c_size_t(), C.c_size_t(), C.c_int()
         lib.eagcn_model_atom_rep(self.index.ref(), C.byref(m), C.byref(xo), C.byref(po), C.byref(ld))
         T = self.index.T
@@ -295,48 +286,33 @@ class GraphRunner:
             m.aux_stream = self.aux.cuda_stream
         return m
 
-    def _grads_struct(self):
-        plan = self.plan
-        base = self.flat_acc.data_ptr()
-
-        def gptr(i):
-            return base + 4 * plan.offsets[i]
-        lg = (L.LayerGrads * len(plan.layers))()
-        for l, (layer, (start, ave)) in enumerate(zip(plan.layers, plan.layer_slices)):
-            g = lg[l]
-            for k in range(layer.K):
-                i = start + 6 * k
-                g.datt_w[k], g.dself_r[k], g.dW[k] = gptr(i), gptr(i + 1), gptr(i + 2)
-                g.dbias[k], g.dgamma[k], g.dbeta[k] = gptr(i + 3), gptr(i + 4), gptr(i + 5)
-            g.dave_w = gptr(ave) if ave is not None else None
-        hg = L.HeadGrads()
-        for j, name in enumerate(('d_den1_w', 'd_den2_w', 'd_den3_w', 'd_gbn_w', 'd_gbn_b', 'd_bn1_w', 'd_bn1_b',
-                                  'd_bn2_w', 'd_bn2_b')):
-            setattr(hg, name, gptr(plan.head_start + j))
-        self.lg, self.hg = lg, hg
-
     def stale(self):
         """Parameter / buffer storage moved (e.g. .to()): the captured pointers are no longer valid."""
         return [t.data_ptr() for t in self.plan._ptr_tensors] != self.ptrs
 
     # -- the two launch sequences --------------------------------------------------------------------
+    def _size_ptr(self):
+        """The current slot's molecule sizes (molfp_mode='ave'); null for the sum read-out."""
+        return _ptr(self.size_static[self.cur]) if self.plan.molfp else C.c_void_p(0)
+
     def _call_forward(self):
         lib = L.load()
         if not torch.cuda.is_current_stream_capturing():
             self.fwd_issued += 1                              # (a captured forward counts when its graph is replayed)
             self.starts_issued += 1
-        size_ptr = _ptr(self.size_static[self.cur]) if self.plan.molfp else C.c_void_p(0)
-        L.check(lib.eagcn_model_forward(self.index.ref(), C.byref(self.cms[self.cur]), C.c_void_p(0), size_ptr,
+        L.check(lib.eagcn_model_forward(self.index.ref(), C.byref(self.cms[self.cur]), C.c_void_p(0), self._size_ptr(),
                                         _ptr(self.saved[self.cur]), self.saved_bytes, _ptr(self.scratch), self.scratch_bytes, _ptr(self.out),
                                         _ptr(self.graph_rep), _stream()), 'eagcn_model_forward')
 
-    def _call_backward(self, with_head=1):
-        lib = L.load()
-        size_ptr = _ptr(self.size_static[self.cur]) if self.plan.molfp else C.c_void_p(0)
-        L.check(lib.eagcn_model_backward_range(self.index.ref(), C.byref(self.cms[self.cur]), size_ptr, _ptr(self.saved[self.cur]),
-                                               self.saved_bytes, _ptr(self.scratch), self.scratch_bytes, _ptr(self.dout),
-                                               _ptr(self.dgr), self.lg, C.byref(self.hg), with_head, len(self.plan.layers) - 1, 0,
-                                               _stream()), 'eagcn_model_backward')
+    def _call_backward(self, with_head=1, hi=None, lo=0):
+        """The backward of layers hi .. lo (default: all of them), behind the head's when `with_head`."""
+        what = 'eagcn_model_backward' if hi is None else 'eagcn_model_backward_range'
+        if hi is None:
+            hi = len(self.plan.layers) - 1
+        L.check(L.load().eagcn_model_backward_range(self.index.ref(), C.byref(self.cms[self.cur]), self._size_ptr(),
+                                                    _ptr(self.saved[self.cur]), self.saved_bytes, _ptr(self.scratch), self.scratch_bytes,
+                                                    _ptr(self.dout), _ptr(self.dgr), self.lg, C.byref(self.hg), with_head, hi, lo,
+                                                    _stream()), what)
 
     def _capture(self):
         """Capture both sequences (nothing executes during capture).  Called after the first step ran
@@ -389,17 +365,9 @@ class GraphRunner:
                 ev.synchronize()
             meta = self.meta_host[slot].tolist()
             self.meta_event[slot] = None
-            if meta[L.META_BAD_ADJ]:
-                raise L.EagcnHipError('a previous batch held %d adjacency entries outside {0,1}' % meta[L.META_BAD_ADJ])
-            if meta[L.META_BAD_REL]:
-                raise L.EagcnHipError('a previous batch held %d bonds whose relation channels are not one-hot'
-                                      % meta[L.META_BAD_REL])
-            if meta[L.META_OVERFLOW]:
-                raise L.EagcnHipError('a previous batch packed %d rows, more than row_cap=%d (it was processed as an '
-                                      'empty batch; no memory was overwritten)' % (meta[L.META_OVERFLOW], self.slots[0].T))
-            if meta[L.META_EDGE_OVERFLOW]:
-                raise L.EagcnHipError('a previous batch held %d directed bonds, more than edge_cap=%d (it was processed as '
-                                      'an empty batch; no memory was overwritten)' % (meta[L.META_EDGE_OVERFLOW], self.slots[0].E))
+            bad = L.index_error(meta, self.slots[0].T, self.slots[0].E, self.meta_compact[slot])
+            if bad:
+                raise L.EagcnHipError('a previous batch: ' + bad)
 
     def _prepare(self, adj, rels, afm, size, seed, overlap=False, bonds=None, labels=None, dp_scale=None):
         """Everything of a step that reads the caller's tensors (index build, packed input, seeds, sizes, labels of a fused
@@ -451,23 +419,13 @@ class GraphRunner:
         istream = C.c_void_p(side.cuda_stream)
         idx.c.n_logical = int(self.n_in) if self.n_in != idx.N else 0     # row stride of the caller's tensors / logical N
         # ---- everything that reads the caller's tensors: index, packed input, seeds, sizes -----------------
-        if bonds is None:
-            rel_ptrs = (C.c_void_p * idx.K)(*[r.data_ptr() for r in rels])
-            L.check(lib.eagcn_index_build(_ptr(adj), rel_ptrs, idx.ref(), C.c_void_p(self.meta_host[slot].data_ptr()),
-                                          istream), 'eagcn_index_build')
-        else:                                                 # compact batch: O(bonds) input instead of the dense tensors
-            bm, bi, bj, bc = bonds
-            L.check(lib.eagcn_index_from_bonds(_ptr(bm), _ptr(bi), _ptr(bj), _ptr(bc), bm.numel(), idx.ref(),
-                                               C.c_void_p(self.meta_host[slot].data_ptr()), istream),
-                    'eagcn_index_from_bonds')
-        L.check(lib.eagcn_index_rows(idx.ref(), istream), 'eagcn_index_rows')
+        ops.index_build(idx.c, adj, rels, bonds, self.meta_host[slot], istream, rows=True)
+        self.meta_compact[slot] = bonds is not None
         L.check(lib.eagcn_model_pack_input(idx.ref(), C.byref(self.cms[cur]), _ptr(afm), _ptr(self.saved[cur]),
                                            self.saved_bytes, istream), 'eagcn_model_pack_input')
         sh = self.seeds_host[slot]                            # pinned staging, one per ring slot (async copy source)
-        sn = sh.numpy()                                       # same derivation as ModelPlan.cmodel
-        for l in range(4):
-            sn[l] = (seed + 7919 * (l + 1)) & (2 ** 63 - 1)
-        sn[4] = (seed + 0x51ED27) & (2 ** 63 - 1)
+        sn = sh.numpy()
+        sn[:4], sn[4] = L.dropout_seeds(seed)                 # (the derivation of ModelPlan.cmodel: same masks as the eager engine)
         with torch.cuda.stream(side):
             self.seeds_dev[cur].copy_(sh, non_blocking=True)
             if self.plan.molfp:
@@ -493,16 +451,7 @@ class GraphRunner:
             ev.synchronize()
             meta = self.meta_host[slot].tolist()
             self.meta_event[slot] = None
-            bad = None
-            if meta[L.META_BAD_ADJ]:
-                bad = ('%d bonds are out of range or listed twice' if bonds is not None else
-                       'adjs holds %d entries outside {0,1}') % meta[L.META_BAD_ADJ]
-            elif meta[L.META_BAD_REL]:
-                bad = '%d bonded (i,j,view) positions are not one-hot over the relation channels' % meta[L.META_BAD_REL]
-            elif meta[L.META_OVERFLOW]:
-                bad = 'the batch packs %d rows, more than row_cap=%d' % (meta[L.META_OVERFLOW], idx.T)
-            elif meta[L.META_EDGE_OVERFLOW]:
-                bad = 'the batch holds %d directed bonds, more than edge_cap=%d' % (meta[L.META_EDGE_OVERFLOW], idx.E)
+            bad = L.index_error(meta, idx.T, idx.E, bonds is not None)
             if bad:
                 if overlap:
                     main.wait_stream(side)
@@ -596,7 +545,7 @@ class GraphRunner:
         m_first = L.Model.from_buffer_copy(self.cms[cur])
         m_rest = L.Model.from_buffer_copy(self.cms[cur])
         m_rest.wait_flag = m_rest.start_signal = m_rest.fwd_signal = None
-        size_ptr = _ptr(self.size_static[cur]) if self.plan.molfp else C.c_void_p(0)
+        size_ptr = self._size_ptr()
         key = (cur, int(steps), steps and baseline is not None)
 
         def run():
@@ -695,8 +644,7 @@ class GraphRunner:
         sl.loss = self.loss_static[cur].data_ptr()
         sl.scale = self.scale_static[cur].data_ptr() if scaled else None       # data-parallel global normalisation (parallel.dp_loss_scale)
         sl.dout = self.dout.data_ptr()
-        size_ptr = _ptr(self.size_static[cur]) if self.plan.molfp else C.c_void_p(0)
-        L.check(lib.eagcn_model_forward_step(self.index.ref(), C.byref(self.cms[cur]), C.c_void_p(0), size_ptr, _ptr(self.saved[cur]),
+        L.check(lib.eagcn_model_forward_step(self.index.ref(), C.byref(self.cms[cur]), C.c_void_p(0), self._size_ptr(), _ptr(self.saved[cur]),
                                              self.saved_bytes, _ptr(self.scratch), self.scratch_bytes, _ptr(self.out), _ptr(self.graph_rep),
                                              C.byref(sl), _ptr(self.dgr), C.byref(self.hg), _stream()), 'eagcn_model_forward_step')
 
@@ -704,23 +652,15 @@ class GraphRunner:
         """The backward with the gradient average inside: head + upper layers, then the all-reduce of their bucket of the flat
         gradient buffer is STARTED (asynchronously: under capture a branch of the graph), the first layer's backward runs
         beside it, and its own (small) bucket follows.  One bucket when the model has a single layer."""
-        lib = L.load()
         nl = len(self.plan.layers)
         if nl < 2:
             self._call_backward(with_head)
             comm.start(self.flat_acc).wait()
             return
-        size_ptr = _ptr(self.size_static[self.cur]) if self.plan.molfp else C.c_void_p(0)
-
-        def part(with_head, hi, lo):
-            L.check(lib.eagcn_model_backward_range(self.index.ref(), C.byref(self.cms[self.cur]), size_ptr, _ptr(self.saved[self.cur]),
-                                                   self.saved_bytes, _ptr(self.scratch), self.scratch_bytes, _ptr(self.dout),
-                                                   _ptr(self.dgr), self.lg, C.byref(self.hg), with_head, hi, lo, _stream()),
-                    'eagcn_model_backward_range')
-        part(with_head, nl - 1, 1)
+        self._call_backward(with_head, nl - 1, 1)
         cut = self.plan.offsets[self.plan.layer_slices[1][0]]      # first gradient of the second layer: [0, cut) = layer 1
         upper = comm.start(self.flat_acc[cut:])
-        part(0, 0, 0)
+        self._call_backward(0, 0, 0)
         upper.wait()
         comm.start(self.flat_acc[:cut]).wait()
 

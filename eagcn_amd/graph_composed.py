@@ -26,7 +26,7 @@ import torch
 from . import _lib as L
 from .graph import StaticIndex
 from .losses import _FusedLoss
-from .ops import _ptr
+from .ops import index_build
 
 
 class ComposedRunner:
@@ -57,16 +57,10 @@ class ComposedRunner:
         self.replays = 0
 
     # ---- what reads the caller's tensors (eager) ---------------------------------------------------------------------------
-    def _raise_if_bad(self, when):
-        meta = self.meta_host.tolist()
-        if meta[L.META_BAD_ADJ]:
-            raise L.EagcnHipError('%s batch held %d adjacency entries outside {0,1}' % (when, meta[L.META_BAD_ADJ]))
-        if meta[L.META_BAD_REL]:
-            raise L.EagcnHipError('%s batch held %d bonds whose relation channels are not one-hot' % (when, meta[L.META_BAD_REL]))
-        if meta[L.META_OVERFLOW]:
-            raise L.EagcnHipError('%s batch packed %d rows, more than row_cap=%d' % (when, meta[L.META_OVERFLOW], self.index.T))
-        if meta[L.META_EDGE_OVERFLOW]:
-            raise L.EagcnHipError('%s batch held %d directed bonds, more than edge_cap=%d' % (when, meta[L.META_EDGE_OVERFLOW], self.index.E))
+    def _raise_if_bad(self, prefix=''):
+        bad = L.index_error(self.meta_host.tolist(), self.index.T, self.index.E)
+        if bad:
+            raise L.EagcnHipError(prefix + bad)
 
     def _load(self, adj, rels, afm, size, labels, training):
         lib = L.load()
@@ -76,19 +70,15 @@ class ComposedRunner:
             self.pending.synchronize()
             self.pending = None
             if self.validate != 'sync':
-                self._raise_if_bad('the previous')
+                self._raise_if_bad('the previous batch: ')
         idx = self.index
         B, N = self.key[0], self.key[1]
         if adj.shape != (B, N, N) or afm.shape != self.afm.shape or len(rels) != idx.K:
             raise L.EagcnHipError('batch tensors adjs %s afms %s (%d relation tensors) do not match the captured shape [%d,%d]'
                                   % (tuple(adj.shape), tuple(afm.shape), len(rels), B, N))
         stream = torch.cuda.current_stream(self.device)
-        st = C.c_void_p(stream.cuda_stream)
         idx.c.n_logical = 0
-        rel_ptrs = (C.c_void_p * idx.K)(*[r.data_ptr() for r in rels])
-        L.check(lib.eagcn_index_build(_ptr(adj), rel_ptrs, idx.ref(), C.c_void_p(self.meta_host.data_ptr()), st),
-                'eagcn_index_build')
-        L.check(lib.eagcn_index_rows(idx.ref(), st), 'eagcn_index_rows')
+        index_build(idx.c, adj, rels, None, self.meta_host, C.c_void_p(stream.cuda_stream), rows=True)
         self._keep = (adj, rels)               # (read by the kernels queued above)
         self.afm.copy_(afm, non_blocking=True)
         if size is not None:
@@ -97,11 +87,9 @@ class ComposedRunner:
             self.labels.copy_(labels.reshape(self.labels.shape), non_blocking=True)
         if training:
             base = int(torch.randint(0, 2 ** 62, (1,)).item())          # host generator: no device synchronisation
-            sn = self.seeds_host.numpy()
-            for l in range(4):
-                sn[l] = (base + 7919 * (l + 1)) & (2 ** 63 - 1)
-            sn[4] = (base + 0x51ED27) & (2 ** 63 - 1)
-            self.last_seeds = [int(v) for v in sn[:5]]
+            layer_seeds, head_seed = L.dropout_seeds(base)
+            self.last_seeds = layer_seeds + [head_seed]
+            self.seeds_host.numpy()[:5] = self.last_seeds
             self.seeds.copy_(self.seeds_host, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(stream)
@@ -109,7 +97,7 @@ class ComposedRunner:
         if self.validate == 'sync':
             ev.synchronize()
             self.pending = None
-            self._raise_if_bad('the')
+            self._raise_if_bad()
 
     # ---- the recorded sequence -------------------------------------------------------------------------------------------------
     def _body(self, kind):

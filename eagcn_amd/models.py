@@ -44,6 +44,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from ._lib import structure_code
 from .layers import GAT, Dense, Diff_Pooling, GraphConv_Layer, Vanilla_GCN
 
 
@@ -252,16 +253,7 @@ class EAGCN(nn.Module):
         from . import graph as G
         afms = ops._need_cuda_f32(afms, 'afms')
         if bonds is None:
-            adjs = ops._need_cuda_f32(adjs, 'adjs')
-            rels = [ops._need_cuda_f32(r, 'relation tensor %d' % i) for i, r in enumerate(rels)]
-            B, N = adjs.shape[0], adjs.shape[1]
-            if adjs.dim() != 3 or adjs.shape[2] != N or afms.shape != (B, N, self.n_afeat) or len(rels) != self.K:
-                raise ops.L.EagcnHipError('inconsistent batch tensors: adjs %s afms %s, %d relation tensors'
-                                          % (tuple(adjs.shape), tuple(afms.shape), len(rels)))
-            for i, r in enumerate(rels):
-                if r.dim() != 4 or r.shape[0] != B or r.shape[2] != N or r.shape[3] != N:
-                    raise ops.L.EagcnHipError('relation tensor %d must be [B,C,N,N], got %s' % (i, tuple(r.shape)))
-            channels = tuple(int(r.shape[1]) for r in rels)
+            adjs, rels, B, N, channels = ops.dense_batch(adjs, rels, afms, self.n_afeat, self.K)
             btuple = None
         else:
             B, N, channels = bonds.B, bonds.N, tuple(bonds.channels)
@@ -301,16 +293,10 @@ class EAGCN(nn.Module):
     def _composed_runner(self, adjs, afms, rels, size):
         """Validated dense inputs and the cached graph_composed.ComposedRunner of this batch shape (GAT / pool models)."""
         from .graph_composed import ComposedRunner
-        adjs = ops._need_cuda_f32(adjs, 'adjs')
         afms = ops._need_cuda_f32(afms, 'afms')
         if self.structure in ('GCN', 'GAT'):
             rels = rels[:1]
-        rels = [ops._need_cuda_f32(r, 'relation tensor %d' % i) for i, r in enumerate(rels)]
-        B, N = adjs.shape[0], adjs.shape[1]
-        if adjs.dim() != 3 or adjs.shape[2] != N or afms.shape != (B, N, self.n_afeat) or len(rels) != self.K:
-            raise ops.L.EagcnHipError('inconsistent batch tensors: adjs %s afms %s, %d relation tensors'
-                                      % (tuple(adjs.shape), tuple(afms.shape), len(rels)))
-        channels = tuple(int(r.shape[1]) for r in rels)
+        adjs, rels, B, N, channels = ops.dense_batch(adjs, rels, afms, self.n_afeat, self.K)
         if self.structure not in ('GCN', 'GAT'):
             self._check_channels(channels)
         key = ('composed', B, N, channels)
@@ -420,7 +406,7 @@ class EAGCN(nn.Module):
             return self._graph_forward(adjs, afms, rels, size)       # training step, or eval under no_grad (train.py:130-211)
         self._check_channels([int(r.shape[1]) for r in rels])
         index = ops.BatchIndex(adjs, rels, overlap=self.overlap_index,    # once per batch, shared by all layers
-                               structure={'Concate': 0, 'Weighted_sum': 1}.get(self.structure, -1))
+                               structure=structure_code(self.structure))
         return self._forward_index(index, afms, size)
 
     def forward_compact(self, bonds, afms, size):
@@ -526,7 +512,7 @@ class EAGCN(nn.Module):
             if self.structure == 'GCN':
                 rels = rels[:1]
             self._check_channels([int(r.shape[1]) for r in rels])
-            index = ops.BatchIndex(adjs, rels, structure={'Concate': 0, 'Weighted_sum': 1}.get(self.structure, -1))
+            index = ops.BatchIndex(adjs, rels, structure=structure_code(self.structure))
         plan = self.plan()
         m = ops.L.Model.from_buffer_copy(plan.cmodel(False, 0, self.dropout))
         m.input_packed = 1
@@ -591,7 +577,7 @@ class EAGCN(nn.Module):
         *rels, size = rels_and_size
         if self.structure in ('GCN', 'GAT'):
             rels = rels[:1]
-        index = ops.BatchIndex(adjs, rels, bond_lists=(self.structure == 'GAT'), structure={'Concate': 0, 'Weighted_sum': 1}.get(self.structure, -1))
+        index = ops.BatchIndex(adjs, rels, bond_lists=(self.structure == 'GAT'), structure=structure_code(self.structure))
         return self._forward_composed_index(index, afms, size)
 
     def _forward_composed_index(self, index, afms, size, seeds=None):

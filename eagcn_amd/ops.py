@@ -51,6 +51,43 @@ def _index_stream(device):
     return _index_streams[key]
 
 
+def dense_batch(adj, rels, afms=None, n_afeat=None, K=None):
+    """The shape contract of a dense batch (reference utils.py:575-640): adjs [B,N,N], K relation tensors [B,C_k,N,N] and --
+    where given -- afms [B,N,n_afeat] with the model's K views.  Returns (adj, rels, B, N, channels), the tensors contiguous
+    fp32 device tensors."""
+    adj = _need_cuda_f32(adj, 'adjs')
+    rels = [_need_cuda_f32(r, 'relation tensor %d' % i) for i, r in enumerate(rels)]
+    if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
+        raise L.EagcnHipError('adjs must be [B,N,N], got %s' % (tuple(adj.shape),))
+    B, N, _ = adj.shape
+    if not 1 <= len(rels) <= L.MAX_VIEWS:
+        raise L.EagcnHipError('between 1 and %d relation tensors supported, got %d' % (L.MAX_VIEWS, len(rels)))
+    if afms is not None and (afms.shape != (B, N, n_afeat) or len(rels) != K):
+        raise L.EagcnHipError('inconsistent batch tensors: adjs %s afms %s, %d relation tensors'
+                              % (tuple(adj.shape), tuple(afms.shape), len(rels)))
+    for i, r in enumerate(rels):
+        if r.dim() != 4 or r.shape[0] != B or r.shape[2] != N or r.shape[3] != N:
+            raise L.EagcnHipError('relation tensor %d must be [B,C,N,N] = [%d,C,%d,%d], got %s'
+                                  % (i, B, N, N, tuple(r.shape)))
+    return adj, rels, B, N, tuple(int(r.shape[1]) for r in rels)
+
+
+def index_build(c, adj, rels, bonds, host_meta, stream, rows=False):
+    """Issue the index build of one batch into the Batch struct `c` on `stream`: from the dense tensors (adj, rels), or from
+    `bonds` = (bond_mol, bond_i, bond_j, bond_code) of a compact batch (O(bonds) input instead of the dense tensors); the
+    validity words land in the pinned int32 tensor `host_meta`.  rows=True: eagcn_index_rows behind it on the same stream."""
+    lib = L.load()
+    if bonds is None:
+        rel_ptrs = (C.c_void_p * c.K)(*[r.data_ptr() for r in rels])
+        L.check(lib.eagcn_index_build(_ptr(adj), rel_ptrs, C.byref(c), _ptr(host_meta), stream), 'eagcn_index_build')
+    else:
+        bm, bi, bj, bc = bonds
+        L.check(lib.eagcn_index_from_bonds(_ptr(bm), _ptr(bi), _ptr(bj), _ptr(bc), bm.numel(), C.byref(c), _ptr(host_meta), stream),
+                'eagcn_index_from_bonds')
+    if rows:
+        L.check(lib.eagcn_index_rows(C.byref(c), stream), 'eagcn_index_rows')
+
+
 class ColLayout:
     """Column layout of a packed activation matrix: exact widths + padded widths per segment."""
 
@@ -110,67 +147,38 @@ class BatchIndex:
         only waits for those two kernels and keeps running one step ahead of the GPU.  Default False:
         the side stream first waits for everything queued on the current stream (always safe)."""
         self.structure = int(structure)
-        lib = L.load()
-        adj = _need_cuda_f32(adj, 'adjs')
-        rels = [_need_cuda_f32(r, 'relation tensor %d' % i) for i, r in enumerate(rels)]
-        if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
-            raise L.EagcnHipError('adjs must be [B,N,N], got %s' % (tuple(adj.shape),))
-        B, N, _ = adj.shape
-        K = len(rels)
-        if not 1 <= K <= L.MAX_VIEWS:
-            raise L.EagcnHipError('between 1 and %d relation tensors supported, got %d' % (L.MAX_VIEWS, K))
-        for i, r in enumerate(rels):
-            if r.dim() != 4 or r.shape[0] != B or r.shape[2] != N or r.shape[3] != N:
-                raise L.EagcnHipError('relation tensor %d must be [B,C,N,N] = [%d,C,%d,%d], got %s'
-                                      % (i, B, N, N, tuple(r.shape)))
+        adj, rels, B, N, channels = dense_batch(adj, rels)
         self.rel_vectors = None
         self.bond_lists = bool(bond_lists)
-        self._build(adj, rels, B, N, [int(r.shape[1]) for r in rels], adj.device, overlap, row_cap)
+        self._build(adj, rels, B, N, list(channels), adj.device, overlap, row_cap)
 
     def _build(self, adj, rels, B, N, channels, dev, overlap, row_cap, bonds=None):
         lib = L.load()
         K = len(channels)
         self.device, self.B, self.N, self.K = dev, B, N, K
         self.channels = channels
-        self.ldc = (N + 15) // 16 * 16
         i32 = dict(dtype=torch.int32, device=dev)
         main = torch.cuda.current_stream(dev)
         side = _index_stream(dev)
+        c = L.new_batch(B, N, channels)
+        self.ldc = c.ldc
+        lay, _ = L.index_layout(B, N)
         # buffers written on the side stream are allocated on it (the caching allocator recycles blocks
         # per stream: a block freed on `main` may still be read by kernels queued there)
         with torch.cuda.stream(side):
             self.code = torch.empty((K, B, N, self.ldc), dtype=torch.uint8, device=dev)
-            # one allocation for the small int32 arrays: [deg_bn B*N | nat B | row0 B+1 | tile0 B+1 | meta]
-            blob = torch.empty(B * N + 3 * B + 2 + L.META_WORDS + 2 * B + 2, **i32)
-        o = 0
-        self.deg_bn = blob[o:o + B * N]; o += B * N
-        self.nat = blob[o:o + B]; o += B
-        self.row0 = blob[o:o + B + 1]; o += B + 1
-        self.tile0 = blob[o:o + B + 1]; o += B + 1
-        self.meta = blob[o:o + L.META_WORDS]
+            blob = torch.empty(lay['all'].stop, **i32)         # one allocation for the small int32 arrays
+        self.deg_bn, self.nat, self.row0, self.tile0, self.meta = (blob[lay[n]] for n in ('deg_bn', 'nat', 'row0', 'tile0', 'meta'))
         self._blob = blob
-        c = L.Batch()
-        c.B, c.N, c.K, c.ldc = B, N, K, self.ldc
-        for k in range(K):
-            c.channels[k] = self.channels[k]
-        base = blob.data_ptr()
-        c.code, c.deg_bn, c.nat = self.code.data_ptr(), base, base + 4 * B * N
-        c.row0, c.tile0 = base + 4 * (B * N + B), base + 4 * (B * N + 2 * B + 1)
-        c.meta = base + 4 * (B * N + 3 * B + 2)
+        c.code = self.code.data_ptr()
+        L.point_batch(c, blob.data_ptr())
         for k, v in enumerate(getattr(self, 'rel_vectors', None) or ()):
             c.rel_vec[k], c.rel_c[k] = v.data_ptr(), int(v.shape[1])
-        c.ecnt = base + 4 * (B * N + 3 * B + 2 + L.META_WORDS)
-        c.edge0 = c.ecnt + 4 * B
         c.E = 1 << 30                     # (exact-size edge arrays are allocated once the bond count is known)
         host = _host_meta(dev)
         if not overlap:
             side.wait_stream(main)        # inputs may have been produced by work still queued on `main`
-        sptr = C.c_void_p(side.cuda_stream)
-        if bonds is None:
-            rel_ptrs = (C.c_void_p * K)(*[r.data_ptr() for r in rels])
-            L.check(lib.eagcn_index_build(_ptr(adj), rel_ptrs, C.byref(c), C.c_void_p(host.data_ptr()), sptr),
-                    'eagcn_index_build')
-        else:
+        if bonds is not None:
             bm, bi, bj, bc = bonds
             for t, dt, name in ((bm, torch.int32, 'bond_mol'), (bi, torch.int32, 'bond_i'), (bj, torch.int32, 'bond_j'),
                                 (bc, torch.uint8, 'bond_code')):
@@ -179,19 +187,12 @@ class BatchIndex:
             E = bm.numel()
             if bi.numel() != E or bj.numel() != E or tuple(bc.shape) != (E, K):
                 raise L.EagcnHipError('bond arrays disagree: %d / %d / %d bonds, codes %s' % (E, bi.numel(), bj.numel(), tuple(bc.shape)))
-            L.check(lib.eagcn_index_from_bonds(_ptr(bm), _ptr(bi), _ptr(bj), _ptr(bc), E, C.byref(c),
-                                               C.c_void_p(host.data_ptr()), sptr), 'eagcn_index_from_bonds')
+        index_build(c, adj, rels, bonds, host, C.c_void_p(side.cuda_stream))
         side.synchronize()                # waits for the index kernels only, not for the main stream's backlog
         meta = host.tolist()
-        if meta[L.META_BAD_ADJ] and bonds is not None:
-            raise L.EagcnHipError('%d bonds are out of range or listed twice' % meta[L.META_BAD_ADJ])
-        if meta[L.META_BAD_ADJ]:
-            raise L.EagcnHipError('adjs holds %d entries outside {0,1}: the hot path requires a 0/1 '
-                                  'adjacency (reference neural_fp.py:85,109-110)' % meta[L.META_BAD_ADJ])
-        if meta[L.META_BAD_REL]:
-            raise L.EagcnHipError('%d bonded (i,j,view) positions are not one-hot over the relation channels '
-                                  '(reference neural_fp.py:111-120); build the model with relations=\'general\' for relation '
-                                  'tensors with arbitrary channel values (layers.py:82)' % meta[L.META_BAD_REL])
+        bad = L.index_error(meta, compact=bonds is not None)
+        if bad:
+            raise L.EagcnHipError(bad)
         self.T, self.n_max, self.n_tiles = meta[L.META_T], meta[L.META_NMAX], meta[L.META_NTILES]
         self.n_edges = meta[L.META_NEDGE]
         self.rows = self.T                                   # exact packed row count
@@ -202,24 +203,17 @@ class BatchIndex:
             self.n_tiles = B * ((N + 15) // 16)
         T = self.T
         main.wait_stream(side)            # everything below (and every consumer) runs on `main`
-        # [row_info 4T | tile_info 4*n_tiles (both 16-byte aligned) | row_mol | row_loc | row_deg | row_m(f32) | tile_mol]
-        nt = self.n_tiles
-        rows = torch.empty(8 * T + 5 * nt, **i32)
-        o = 4 * T + 4 * nt
-        self.row_mol, self.row_loc, self.row_deg = rows[o:o + T], rows[o + T:o + 2 * T], rows[o + 2 * T:o + 3 * T]
-        self.row_m = rows[o + 3 * T:o + 4 * T].view(torch.float32)
-        self.tile_mol = rows[o + 4 * T:]
+        _, lay = L.index_layout(B, N, T, self.n_tiles)
+        rows = torch.empty(lay['all'].stop, **i32)
+        self.row_mol, self.row_loc, self.row_deg, self.tile_mol = (rows[lay[n]] for n in ('row_mol', 'row_loc', 'row_deg', 'tile_mol'))
+        self.row_m = rows[lay['row_m']].view(torch.float32)
         self._rows = rows
         c.T, c.n_max, c.n_tiles = T, self.n_max, self.n_tiles
         c.t_hint = int(self.rows)                            # (exact here; with a row_cap the buffers are larger than the batch)
-        rb = rows.data_ptr()
-        c.row_info, c.tile_info = rb, rb + 16 * T
-        ob = rb + 4 * o
-        c.row_mol, c.row_loc, c.row_deg, c.row_m, c.tile_mol = ob, ob + 4 * T, ob + 8 * T, ob + 12 * T, ob + 16 * T
         self.E = max(int(self.n_edges), 1)
         self._ptrs = torch.zeros(L.bond_ptrs_len(T, B), **i32)
         self._edges = torch.empty(6 * self.E + 2, **i32)
-        L.set_bond_lists(c, base + 4 * (B * N + 3 * B + 2 + L.META_WORDS), self._ptrs, self._edges, self.E)
+        L.point_batch(c, blob.data_ptr(), rows.data_ptr(), self._ptrs, self._edges, self.E)
         # bond lists: the GAT layers, and the bond-list form of the aggregation where the library picks it (csrc/lagg.hip)
         if lib.eagcn_agg_wants_bond_lists_for(B, N, int(getattr(self, 'structure', -1))):
             self.bond_lists = True
@@ -320,7 +314,7 @@ class LayerSpec:
     """Static description of one multi-view layer (what the C struct needs besides pointers)."""
 
     def __init__(self, structure, widths, in_layout, dropout, bn_eps=1e-5, bn_momentum=0.1):
-        self.structure = {'Concate': L.STRUCT_CONCATE, 'Weighted_sum': L.STRUCT_WEIGHTED}[structure]
+        self.structure = L.STRUCTURES[structure]
         self.structure_name = structure
         self.widths = [int(w) for w in widths]
         self.K = len(self.widths)
@@ -353,6 +347,26 @@ class LayerSpec:
 _PARAM_KEYS = ('att_w', 'self_r', 'W', 'bias', 'gamma', 'beta')
 
 
+def _layer_views(K, flat, buffers):
+    """The K per-view dicts LayerSpec.cparams takes, from the flat parameter list (six per view, _PARAM_KEYS order) and the
+    (running_mean, running_var) pairs."""
+    views = []
+    for k in range(K):
+        v = {name: flat[k * 6 + i] for i, name in enumerate(_PARAM_KEYS)}
+        v['run_mean'], v['run_var'] = buffers[k]
+        views.append(v)
+    return views
+
+
+def _layer_bufs(x, P, Y, rscale, bn, scratch, xout=None, pad_row=None):
+    w = L.LayerBufs()
+    w.x, w.P, w.Y, w.rscale, w.bn = x.data_ptr(), P.data_ptr(), Y.data_ptr(), rscale.data_ptr(), bn.data_ptr()
+    if xout is not None:
+        w.xout, w.pad_row = xout.data_ptr(), pad_row.data_ptr()
+    w.scratch, w.scratch_bytes = scratch.data_ptr(), scratch.numel()
+    return w
+
+
 class _LayerFn(torch.autograd.Function):
     """x_packed, parameters -> (xout_packed, pad_row).  One C call forward, one backward."""
 
@@ -363,20 +377,18 @@ class _LayerFn(torch.autograd.Function):
         x = x.contiguous()
         if x.shape != (index.T, spec.in_layout.ld):
             raise L.EagcnHipError('packed input is %s, expected %s' % (tuple(x.shape), (index.T, spec.in_layout.ld)))
-        views = []
-        for k in range(K):
-            v = {name: flat[k * 6 + i] for i, name in enumerate(_PARAM_KEYS)}
-            for name, t in v.items():
+        views = _layer_views(K, flat, buffers)
+        for k, v in enumerate(views):
+            for name in _PARAM_KEYS:
+                t = v[name]
                 if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
                     raise L.EagcnHipError('parameter %s of view %d must be a contiguous fp32 device tensor' % (name, k))
-            v['run_mean'], v['run_var'] = buffers[k]
             fin = spec.in_layout.width
             if tuple(v['W'].shape) != (fin, spec.widths[k]):
                 raise L.EagcnHipError('view %d weight is %s, expected %s' % (k, tuple(v['W'].shape), (fin, spec.widths[k])))
             if v['att_w'].numel() != index.channels[k]:
                 raise L.EagcnHipError('view %d attention weight has %d channels, relation tensor has %d'
                                       % (k, v['att_w'].numel(), index.channels[k]))
-            views.append(v)
         p = spec.cparams(training, seed, views, ave_w)
         dev, T, fp = x.device, index.T, spec.fp
         f32 = dict(dtype=torch.float32, device=dev)
@@ -388,9 +400,7 @@ class _LayerFn(torch.autograd.Function):
         pad_row = torch.empty(spec.out_layout.ld, **f32)
         nbytes = lib.eagcn_layer_fwd_scratch_bytes(index.ref(), C.byref(p))
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        w = L.LayerBufs()
-        w.x, w.P, w.Y, w.rscale, w.bn = x.data_ptr(), P.data_ptr(), Y.data_ptr(), rscale.data_ptr(), bn.data_ptr()
-        w.xout, w.pad_row, w.scratch, w.scratch_bytes = xout.data_ptr(), pad_row.data_ptr(), scratch.data_ptr(), nbytes
+        w = _layer_bufs(x, P, Y, rscale, bn, scratch, xout, pad_row)
         L.check(lib.eagcn_layer_forward(index.ref(), C.byref(p), C.byref(w), _stream()), 'eagcn_layer_forward')
         ctx.index, ctx.spec, ctx.training, ctx.seed, ctx.buffers = index, spec, training, seed, buffers
         ctx.save_for_backward(x, P, Y, rscale, bn, ave_w, *flat)
@@ -404,12 +414,7 @@ class _LayerFn(torch.autograd.Function):
         index, spec = ctx.index, ctx.spec
         x, P, Y, rscale, bn, ave_w, *flat = ctx.saved_tensors
         K = spec.K
-        views = []
-        for k in range(K):
-            v = {name: flat[k * 6 + i] for i, name in enumerate(_PARAM_KEYS)}
-            v['run_mean'], v['run_var'] = ctx.buffers[k]
-            views.append(v)
-        p = spec.cparams(ctx.training, ctx.seed, views, ave_w)
+        p = spec.cparams(ctx.training, ctx.seed, _layer_views(K, flat, ctx.buffers), ave_w)
         dev = x.device
         dxout = dxout.contiguous()
         grads = [torch.empty_like(t) for t in flat]
@@ -424,9 +429,7 @@ class _LayerFn(torch.autograd.Function):
         dx = torch.empty_like(x) if need_dx else None
         nbytes = lib.eagcn_layer_bwd_scratch_bytes(index.ref(), C.byref(p))
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        w = L.LayerBufs()
-        w.x, w.P, w.Y, w.rscale, w.bn = x.data_ptr(), P.data_ptr(), Y.data_ptr(), rscale.data_ptr(), bn.data_ptr()
-        w.scratch, w.scratch_bytes = scratch.data_ptr(), nbytes
+        w = _layer_bufs(x, P, Y, rscale, bn, scratch)
         dpad_ptr = C.c_void_p(0)
         if spec.structure == L.STRUCT_WEIGHTED and dpad is not None:
             dpad = dpad.contiguous()
@@ -440,6 +443,15 @@ def layer_forward(index, spec, training, seed, buffers, x, ave_w, flat_params):
     return _LayerFn.apply(index, spec, training, seed, buffers, x, ave_w, *flat_params)
 
 
+def _gat_params(fin, ld_in, F, training, seed, dropout, att_dropout, alpha, W, a):
+    p = L.GatParams()
+    p.fin, p.ld_in, p.F, p.training = fin, ld_in, F, int(bool(training))
+    p.alpha, p.att_dropout, p.dropout = float(alpha), float(att_dropout), float(dropout)
+    p.seed, p.seed_dev = _seed_fields(seed)
+    p.W, p.a = W.data_ptr(), a.data_ptr()
+    return p
+
+
 class _GatFn(torch.autograd.Function):
     """The GAT baseline layer (reference layers.py:99-203) on packed rows: (x, W, a) -> xout.  One C call each way."""
 
@@ -451,11 +463,7 @@ class _GatFn(torch.autograd.Function):
         x, W, a = x.contiguous(), W.contiguous(), a.contiguous()
         if x.shape != (index.T, ld_in) or tuple(W.shape) != (fin, F) or a.numel() != 2 * F:
             raise L.EagcnHipError('GAT layer: x %s W %s a %s for fin=%d ld=%d F=%d' % (tuple(x.shape), tuple(W.shape), tuple(a.shape), fin, ld_in, F))
-        p = L.GatParams()
-        p.fin, p.ld_in, p.F, p.training = fin, ld_in, F, int(bool(training))
-        p.alpha, p.att_dropout, p.dropout = float(alpha), float(att_dropout), float(dropout)
-        p.seed, p.seed_dev = _seed_fields(seed)
-        p.W, p.a = W.data_ptr(), a.data_ptr()
+        p = _gat_params(fin, ld_in, F, training, seed, dropout, att_dropout, alpha, W, a)
         Fp = (F + 15) // 16 * 16
         f32 = dict(dtype=torch.float32, device=x.device)
         h = torch.empty((index.T, Fp), **f32)
@@ -471,13 +479,8 @@ class _GatFn(torch.autograd.Function):
     def backward(ctx, dxout):
         lib = L.load()
         x, W, a, h, s12, xout = ctx.saved_tensors
-        fin, ld_in, F, training, seed, dropout, att_dropout, alpha = ctx.p_args
-        index = ctx.index
-        p = L.GatParams()
-        p.fin, p.ld_in, p.F, p.training = fin, ld_in, F, int(bool(training))
-        p.alpha, p.att_dropout, p.dropout = float(alpha), float(att_dropout), float(dropout)
-        p.seed, p.seed_dev = _seed_fields(seed)
-        p.W, p.a = W.data_ptr(), a.data_ptr()
+        index, F = ctx.index, ctx.p_args[2]
+        p = _gat_params(*ctx.p_args, W, a)
         dxout = dxout.contiguous()
         dW, da = torch.empty_like(W), torch.empty_like(a)
         dx = torch.empty_like(x) if ctx.needs_input_grad[9] else None
@@ -831,6 +834,26 @@ class ModelPlan:
         return [flat[o:o + n] if len(sh) == 1 else flat[o:o + n].view(sh)
                 for o, n, sh in zip(self.offsets, self.sizes, self.shapes)]
 
+    def grad_structs(self, flat):
+        """(LayerGrads array, HeadGrads) whose pointers are the parameters' slots of the flat fp32 gradient buffer `flat`
+        (laid out by `offsets`): per view att_w, self_r, W, bias, gamma, beta, then ave_w of a Weighted_sum layer; the head's nine
+        from `head_start` in HEAD_PARAMS order."""
+        base = flat.data_ptr()
+
+        def gptr(i):
+            return base + 4 * self.offsets[i]
+        lg = (L.LayerGrads * len(self.layers))()
+        for g, layer, (start, ave) in zip(lg, self.layers, self.layer_slices):
+            for k in range(layer.K):
+                i = start + 6 * k
+                g.datt_w[k], g.dself_r[k], g.dW[k] = gptr(i), gptr(i + 1), gptr(i + 2)
+                g.dbias[k], g.dgamma[k], g.dbeta[k] = gptr(i + 3), gptr(i + 4), gptr(i + 5)
+            g.dave_w = gptr(ave) if ave is not None else None
+        hg = L.HeadGrads()
+        for j, name in enumerate(HEAD_GRADS):
+            setattr(hg, name, gptr(self.head_start + j))
+        return lg, hg
+
     def flush_nbt(self):
         """Write the batches counted on the host by graph mode into the num_batches_tracked buffers (they are not
         read by the computation: momentum is a number, reference layers.py:403).  Called by EAGCN.state_dict()."""
@@ -849,17 +872,15 @@ class ModelPlan:
             hit = (self._build_cmodel(training, dropout), ptrs)
             self._cm_cache[key] = hit
         m = hit[0]
-        seed = int(seed)
-        m.head_seed = (seed + 0x51ED27) & (2 ** 63 - 1)
-        for l in range(len(self.layers)):
-            m.layer[l].seed = (seed + 7919 * (l + 1)) & (2 ** 63 - 1)
+        layer_seeds, m.head_seed = L.dropout_seeds(seed, len(self.layers))
+        for l, s in enumerate(layer_seeds):
+            m.layer[l].seed = s
         return m
 
     def _build_cmodel(self, training, dropout):
-        seed = 0
         m = L.Model()
         m.n_layers, m.molfp_mode, m.training = len(self.layers), self.molfp, int(bool(training))
-        m.head_seed = (int(seed) + 0x51ED27) & (2 ** 63 - 1)
+        layer_seeds, m.head_seed = L.dropout_seeds(0, len(self.layers))     # (cmodel re-seeds the cached struct per call)
         for l, (layer, spec) in enumerate(zip(self.layers, self.specs)):
             spec.dropout = float(layer.dropout)
             views = []
@@ -869,7 +890,7 @@ class ModelPlan:
                               'bias': blk.graph_conv.bias, 'gamma': bn.weight, 'beta': bn.bias,
                               'run_mean': bn.running_mean, 'run_var': bn.running_var})
             ave = layer.ave.weight if layer.structure == 'Weighted_sum' else None
-            m.layer[l] = spec.cparams(training, (int(seed) + 7919 * (l + 1)) & (2 ** 63 - 1), views, ave)
+            m.layer[l] = spec.cparams(training, layer_seeds[l], views, ave)
         fill_head_params(m.head, self.head, dropout)
         m.fuse_readout = int(self.fuse_readout)
         if self.stats is not None:                    # sync-BatchNorm: cross-rank sums through eagcn_amd.parallel.StatsAllReducer
@@ -957,23 +978,7 @@ class _ModelFn(torch.autograd.Function):
                 return (None,) * 7 + (dafm, None)
             return (None,) * 7 + (dafm,) + (None,) * (1 + len(plan.params))
         flat = torch.zeros(plan.offsets[-1], dtype=torch.float32, device=dev)
-        base = flat.data_ptr()
-
-        def gptr(i):
-            return base + 4 * plan.offsets[i]
-        lg = (L.LayerGrads * len(plan.layers))()
-        for l, (layer, (start, ave)) in enumerate(zip(plan.layers, plan.layer_slices)):
-            g = lg[l]
-            for k in range(layer.K):
-                i = start + 6 * k
-                g.datt_w[k], g.dself_r[k], g.dW[k] = gptr(i), gptr(i + 1), gptr(i + 2)
-                g.dbias[k], g.dgamma[k], g.dbeta[k] = gptr(i + 3), gptr(i + 4), gptr(i + 5)
-            g.dave_w = gptr(ave) if ave is not None else None
-        hg = L.HeadGrads()
-        hs = plan.head_start
-        for j, name in enumerate(('d_den1_w', 'd_den2_w', 'd_den3_w', 'd_gbn_w', 'd_gbn_b', 'd_bn1_w', 'd_bn1_b',
-                                  'd_bn2_w', 'd_bn2_b')):
-            setattr(hg, name, gptr(hs + j))
+        lg, hg = plan.grad_structs(flat)
         dafm = None
         if ctx.want_afm:                               # the same backward, layer 0 also forming d(input)
             dafm = torch.empty(ctx.afm_shape, dtype=torch.float32, device=dev)
@@ -1052,6 +1057,7 @@ def model_forward(plan, index, holder, training, seed, dropout, size, afm, direc
 # ------------------------------------------------------------------------------------------------
 HEAD_PARAMS = (('den1', 'weight'), ('den2', 'weight'), ('den3', 'weight'), ('Graph_BN', 'weight'), ('Graph_BN', 'bias'),
                ('bn_den1', 'weight'), ('bn_den1', 'bias'), ('bn_den2', 'weight'), ('bn_den2', 'bias'))
+HEAD_GRADS = tuple(name for name, _ in L.HeadGrads._fields_)       # their gradient fields, in the same order (eagcn_head_grads)
 
 
 class _HeadFn(torch.autograd.Function):
@@ -1102,8 +1108,7 @@ class _HeadFn(torch.autograd.Function):
         dgr = dgraph_rep.contiguous() if dgraph_rep is not None else None
         grads = [torch.empty_like(p) for p in params]
         hg = L.HeadGrads()
-        for name, t in zip(('d_den1_w', 'd_den2_w', 'd_den3_w', 'd_gbn_w', 'd_gbn_b', 'd_bn1_w', 'd_bn1_b', 'd_bn2_w', 'd_bn2_b'),
-                           grads):
+        for name, t in zip(HEAD_GRADS, grads):
             setattr(hg, name, t.data_ptr())
         dg = torch.empty_like(g)
         scratch = _scratch(dev, lib.eagcn_head_scratch_bytes(C.byref(hp), B))

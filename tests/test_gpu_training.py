@@ -5,7 +5,9 @@ loss curve, parameters, BatchNorm running statistics, num_batches_tracked, valid
 Training is a chaotic map: the fp32 CPU oracle itself leaves the fp64 trajectory by 1e-4 .. 2e-2 within 50 Adam steps
 (tests/probe_train_drift.py), so the yardstick is the fp64 oracle and the bar is the reference's own fp32 drift, STEP BY
 STEP and TENSOR BY TENSOR: while the fp32 oracle's copy is within 1e-4 of the fp64 trajectory, the HIP copy may be at most
-as far from it as the oracle is -- compared as distributions over the tensors (median x3, worst x10); after that Adam has amplified rounding noise and nothing is compared."""
+as far from it as the oracle is -- compared as distributions over the tensors (median x3, worst x10); after that Adam has amplified rounding noise and nothing is compared.
+"The fp32 oracle" is four runs -- the oracle and three copies started one unit in the last place away -- and its drift the largest
+of theirs: where the trajectory passes a relu kink a single run's side of it, and with it the bar, depended on the host CPU."""
 import numpy as np
 import pytest
 import torch
@@ -39,7 +41,20 @@ def test_fifty_adam_steps_track_the_oracle(task, optim):
     ref64 = RefEAGCN(9, 24, w1, w2, 32, 16, T, 0.0, n_layers=2).double()
     ref64.load_state_dict({k: v.double() for k, v in ref.state_dict().items()})
     cpu64 = [([t.double() if t.is_floating_point() else t for t in d], l) for d, l in cpu]
-    opt_r = torch.optim.Adam(ref.parameters(), lr=5e-4, weight_decay=1e-4)
+    # The fp32 yardstick is an ENSEMBLE of oracle runs: the oracle as initialised, and copies whose initial parameters are moved
+    # by at most one unit in the last place (seeded).  One fp32 run is one sample of where fp32 arithmetic leaves the fp64
+    # trajectory: in the `class` case an activation sits on its relu kink around step 9, and which side a run takes is decided by
+    # the last bit -- of four one-ulp copies, three leave the fp64 trajectory there (as the HIP run does) and one follows it until
+    # step 26; the unperturbed oracle does the one or the other depending on the host CPU's kernels.  A bar taken from a
+    # single run therefore depended on the machine the test ran on.
+    def ulp_copy(seed):
+        m = RefEAGCN(9, 24, w1, w2, 32, 16, T, 0.0, n_layers=2)
+        g = torch.Generator().manual_seed(seed)
+        m.load_state_dict({k: v * (1 + 2.0 ** -23 * torch.randint(-1, 2, v.shape, generator=g).float()) if v.is_floating_point() else v
+                           for k, v in ref.state_dict().items()})
+        return m
+    refs = [ref] + [ulp_copy(seed) for seed in (1, 2, 3)]
+    opt_rs = [torch.optim.Adam(m.parameters(), lr=5e-4, weight_decay=1e-4) for m in refs]
     opt_x = torch.optim.Adam(ref64.parameters(), lr=5e-4, weight_decay=1e-4)
     if optim == 'flat':
         from eagcn_amd.optim import FlatAdam
@@ -69,17 +84,17 @@ def test_fifty_adam_steps_track_the_oracle(task, optim):
         return {k: (sd[k].double().cpu() - v).abs().max().item() / max(v.abs().max().item(), 1e-3)
                 for k, v in sd_x.items() if not noise_key(k)}
 
-    # Trajectory parity, step by step and tensor by tensor: as long as the fp32 ORACLE's copy of a tensor stays within 1e-4 of
-    # the fp64 trajectory the comparison means something, and there the HIP run's copy must be as close to fp64 as the fp32
-    # oracle's is (three times its drift + 1e-5 of the tensor's scale: two fp32 arithmetics round differently, and a one-element
-    # tensor such as self_r moves by whole multiples of Adam's step).  A tensor the oracle has lost (Adam turns
-    # rounding noise in a near-zero gradient into +-lr steps) is not compared any more from that step on (VERDICT round 2,
-    # weak-3: the old bound admitted 22 % of a parameter's scale after 50 steps).
-    loss_r, loss_x, loss_h = [], [], []
+    # Trajectory parity, step by step and tensor by tensor: as long as EVERY fp32 oracle run's copy of a tensor stays within 1e-4
+    # of the fp64 trajectory the comparison means something, and there the HIP run's copy must be as close to fp64 as the fp32
+    # oracle's is (its drift = the largest of the runs'; three times it + 1e-5 of the tensor's scale: two fp32 arithmetics round
+    # differently, and a one-element tensor such as self_r moves by whole multiples of Adam's step).  A tensor an oracle run has
+    # lost (Adam turns rounding noise in a near-zero gradient into +-lr steps) is not compared any more from that step on
+    # (the old bound admitted 22 % of a parameter's scale after 50 steps).
+    loss_rs, loss_x, loss_h = [[] for _ in refs], [], []
     alive, window = None, {}
     pworst, worst_ratio, n_cmp = 0.0, 0.0, 0
     for step in range(50):
-        for m, o, data, acc in ((ref, opt_r, cpu, loss_r), (ref64, opt_x, cpu64, loss_x)):
+        for m, o, data, acc in [(m, o, cpu, acc) for m, o, acc in zip(refs, opt_rs, loss_rs)] + [(ref64, opt_x, cpu64, loss_x)]:
             d, l = data[step % 4]
             o.zero_grad()
             out, _, _ = m(*d)
@@ -91,7 +106,8 @@ def test_fifty_adam_steps_track_the_oracle(task, optim):
         loss_h.append(float(training.train_step(hip, opt_h, dd, ll, task, bw_dev).detach()))
         if alive is None or alive:
             sd_x = ref64.state_dict()
-            d_r = drifts(ref.state_dict(), sd_x)
+            d_rs = [drifts(m.state_dict(), sd_x) for m in refs]
+            d_r = {k: max(d[k] for d in d_rs) for k in d_rs[0]}
             if alive is None:
                 alive = set(d_r)
             alive = {k for k in alive if d_r[k] < 1e-4}
@@ -111,7 +127,7 @@ def test_fifty_adam_steps_track_the_oracle(task, optim):
                 pworst = max(pworst, hs[-1])
                 worst_ratio = max(worst_ratio, hs[-1] / max(rs[-1], 1e-6))
                 if len(alive) == len(d_r):             # the loss is compared while the oracle tracks EVERY tensor
-                    dl_r, dl_h = abs(loss_r[-1] - loss_x[-1]), abs(loss_h[-1] - loss_x[-1])
+                    dl_r, dl_h = max(abs(acc[-1] - loss_x[-1]) for acc in loss_rs), abs(loss_h[-1] - loss_x[-1])
                     assert dl_h <= 3.0 * dl_r + 1e-5 * max(abs(loss_x[-1]), 1.0), (step, loss_h[-1], loss_x[-1], dl_r)
     wl = sorted(window.values())
     print('trajectory parity [%s]: %d tensor-steps compared; per-tensor windows min %d / median %d / max %d of 50 steps; worst HIP '

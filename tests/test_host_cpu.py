@@ -374,3 +374,111 @@ def test_bond_list_buffers_are_laid_out_without_overlap():
         assert c.nbr == elo and c.tnbr == elo + 4 * E
         assert c.ecode % 8 == 0 and c.ecode >= c.tnbr + 4 * E and c.tcode == c.ecode + 8 * E and c.tcode + 8 * E <= ehi
         assert c.ecnt == 4096 and c.edge0 == 4096 + 4 * B
+
+
+@pytest.mark.parametrize('N', [1, 17, 132])
+def test_index_buffers_are_laid_out_as_the_kernels_read_them(N):
+    """_lib.index_layout / point_batch, the one home of the batch-index layout (ops.BatchIndex and graph.StaticIndex both go
+    through them): every pointer of a filled Batch against the arithmetic written out here, no two regions overlapping, the
+    totals of the two allocations."""
+    from eagcn_amd import _lib as L
+    for T, B, E in ((4809, 256, 10331), (7, 3, 5), (262144, 1024, 1100000), (1, 1, 1)):
+        nt = B * -(-N // 16)
+        blob_lay, rows_lay = L.index_layout(B, N, T, nt)
+        assert blob_lay['all'] == slice(0, B * N + 5 * B + 4 + 16) and rows_lay['all'] == slice(0, 8 * T + 5 * nt)
+        assert L.index_layout(B, N)[0] == blob_lay                     # (the blob is known before the row count is)
+        ptrs = torch.zeros(L.bond_ptrs_len(T, B), dtype=torch.int32)
+        edges = torch.zeros(6 * E + 2, dtype=torch.int32)
+        c = L.new_batch(B, N, [3, 2])
+        assert (c.B, c.N, c.K, c.ldc, list(c.channels)[:3]) == (B, N, 2, -(-N // 16) * 16, [3, 2, 0])
+        c.T, c.n_tiles = T, nt
+        base, rb = 1 << 20, 1 << 40
+        L.point_batch(c, base, rb, ptrs, edges, E)
+        assert c.deg_bn == base and c.nat == base + 4 * B * N and c.row0 == base + 4 * (B * N + B)
+        assert c.tile0 == base + 4 * (B * N + 2 * B + 1) and c.meta == base + 4 * (B * N + 3 * B + 2)
+        assert c.ecnt == c.meta + 64 and c.edge0 == c.ecnt + 4 * B
+        assert c.row_info == rb and c.tile_info == rb + 16 * T
+        assert c.row_mol == rb + 16 * T + 16 * nt and c.row_loc == c.row_mol + 4 * T and c.row_deg == c.row_loc + 4 * T
+        assert c.row_m == c.row_deg + 4 * T and c.tile_mol == c.row_m + 4 * T
+        assert c.E == E and c.row_ptr == ptrs.data_ptr() and c.nbr == edges.data_ptr()
+        for lay, start, sizes in ((blob_lay, base, dict(deg_bn=B * N, nat=B, row0=B + 1, tile0=B + 1, meta=16, ecnt=B, edge0=B + 1)),
+                                  (rows_lay, rb, dict(row_info=4 * T, tile_info=4 * nt, row_mol=T, row_loc=T, row_deg=T, row_m=T,
+                                                      tile_mol=nt))):
+            spans = sorted((getattr(c, n), getattr(c, n) + 4 * w) for n, w in sizes.items())
+            assert spans[0][0] == start and spans[-1][1] == start + 4 * (lay['all'].stop - (lay is blob_lay))   # (one spare word)
+            assert all(a[1] == b[0] for a, b in zip(spans, spans[1:]))          # back to back: no overlap, no hole
+            assert all((lay[n].start, lay[n].stop - lay[n].start) == ((getattr(c, n) - start) // 4, w) for n, w in sizes.items())
+        # the two-phase use of the eager index: the blob first (row count still unknown), the rows later
+        c2 = L.new_batch(B, N, [3, 2])
+        L.point_batch(c2, base)
+        assert (c2.meta, c2.ecnt, c2.edge0, c2.row_info, c2.row_ptr) == (c.meta, c.ecnt, c.edge0, None, None)
+
+
+def _small_model(cls):
+    return cls(7, 24, *[8, 6, 4, 4, 5], *[10, 7, 5, 6, 4], 16, 8, 3, 0.3, n_layers=2)
+
+
+@pytest.mark.parametrize('seed', [0, 5, 2 ** 62 - 1])
+def test_dropout_seeds_have_one_derivation(seed):
+    from eagcn_amd import Concate_GCN, _lib as L
+    M = 2 ** 63 - 1
+    layers, head = L.dropout_seeds(seed)
+    assert layers == [(seed + 7919 * (l + 1)) & M for l in range(4)] and head == (seed + 0x51ED27) & M
+    assert L.dropout_seeds(seed, 2)[0] == layers[:2]
+    m = _small_model(Concate_GCN).plan().cmodel(True, seed, 0.3)
+    assert [m.layer[l].seed for l in range(2)] == layers[:2] and m.head_seed == head
+    if seed == 5:
+        assert m.layer[1].seed == 15843 and m.head_seed == 5369132          # the values before the derivation had one home
+
+
+@pytest.mark.parametrize('compact', [False, True])
+def test_index_validity_report(compact):
+    from eagcn_amd import _lib as L
+    assert L.index_error([0] * L.META_WORDS, 100, 200, compact) is None
+    assert L.index_error([4809, 132, 99, 0, 0, 777, 0, 0] + [0] * 8, 100, 200, compact) is None     # counts are no errors
+    for word, count in ((L.META_BAD_ADJ, 31), (L.META_BAD_REL, 47), (L.META_OVERFLOW, 4809), (L.META_EDGE_OVERFLOW, 10331)):
+        meta = [0] * L.META_WORDS
+        meta[word] = count
+        msg = L.index_error(meta, row_cap=1234, edge_cap=5678, compact=compact)
+        assert str(count) in msg, msg
+        if word == L.META_BAD_ADJ:
+            assert ('out of range or listed twice' in msg) == compact and ('outside {0,1}' in msg) != compact, msg
+        if word == L.META_BAD_REL:
+            assert 'one-hot' in msg and "relations='general'" in msg, msg
+        if word == L.META_OVERFLOW:
+            assert 'row_cap=1234' in msg, msg
+        if word == L.META_EDGE_OVERFLOW:
+            assert 'edge_cap=5678' in msg, msg
+
+
+@pytest.mark.parametrize('cls', ['Concate_GCN', 'Weighted_GCN'])
+def test_gradient_descriptors_point_into_the_flat_buffer(cls):
+    """ModelPlan.grad_structs: every pointer is the parameter's slot of the flat buffer."""
+    import eagcn_amd
+    from eagcn_amd import ops
+    model = _small_model(getattr(eagcn_amd, cls))
+    plan = model.plan()
+    flat = torch.zeros(plan.offsets[-1], dtype=torch.float32)
+    lg, hg = plan.grad_structs(flat)
+
+    def slot(p):
+        i = [j for j, q in enumerate(plan.params) if q is p]
+        assert len(i) == 1
+        return flat.data_ptr() + 4 * plan.offsets[i[0]]
+    assert len(lg) == 2
+    for g, layer in zip(lg, model.graph_layers()):
+        blocks = list(layer.blocks())
+        assert len(blocks) == 5
+        for k, blk in enumerate(blocks):
+            bn = blk.batch_norm.bn
+            got = (g.datt_w[k], g.dself_r[k], g.dW[k], g.dbias[k], g.dgamma[k], g.dbeta[k])
+            assert got == tuple(slot(p) for p in (blk.att.weight, blk.self_r, blk.graph_conv.weight, blk.graph_conv.bias, bn.weight, bn.bias))
+        assert all(f[k] is None for _, f in ((n, getattr(g, n)) for n, _ in g._fields_ if n != 'dave_w') for k in range(5, 8))
+        if cls == 'Weighted_GCN':
+            assert g.dave_w == slot(layer.ave.weight)
+        else:
+            assert g.dave_w is None
+    assert len(ops.HEAD_GRADS) == len(ops.HEAD_PARAMS) == 9
+    for j, (name, (mn, pn)) in enumerate(zip(ops.HEAD_GRADS, ops.HEAD_PARAMS)):
+        assert getattr(hg, name) == flat.data_ptr() + 4 * plan.offsets[plan.head_start + j] == slot(getattr(getattr(model, mn), pn))
+    assert ops.HEAD_GRADS == ('d_den1_w', 'd_den2_w', 'd_den3_w', 'd_gbn_w', 'd_gbn_b', 'd_bn1_w', 'd_bn1_b', 'd_bn2_w', 'd_bn2_b')

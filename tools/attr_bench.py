@@ -64,17 +64,7 @@ def run_shape(B, steps, warmup, reps):
     dout = torch.randn(B, 12, device='cuda')
     L.check(lib.eagcn_model_pack_input(index.ref(), C.byref(m), ops._ptr(afm), ops._ptr(saved), sb, ops._stream()), 'pack')
     flat = torch.zeros(plan.offsets[-1], dtype=torch.float32, device='cuda')
-    lg = (L.LayerGrads * len(plan.layers))()
-    gp = lambda i: flat.data_ptr() + 4 * plan.offsets[i]
-    for li, (layer, (start, ave)) in enumerate(zip(plan.layers, plan.layer_slices)):
-        for k in range(layer.K):
-            i = start + 6 * k
-            lg[li].datt_w[k], lg[li].dself_r[k], lg[li].dW[k] = gp(i), gp(i + 1), gp(i + 2)
-            lg[li].dbias[k], lg[li].dgamma[k], lg[li].dbeta[k] = gp(i + 3), gp(i + 4), gp(i + 5)
-        lg[li].dave_w = gp(ave) if ave is not None else None
-    hg = L.HeadGrads()
-    for j, name in enumerate(('d_den1_w', 'd_den2_w', 'd_den3_w', 'd_gbn_w', 'd_gbn_b', 'd_bn1_w', 'd_bn1_b', 'd_bn2_w', 'd_bn2_b')):
-        setattr(hg, name, gp(plan.head_start + j))
+    lg, hg = plan.grad_structs(flat)
     nul = C.c_void_p(0)
 
     def fwd():
