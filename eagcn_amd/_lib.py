@@ -215,6 +215,8 @@ SIGNATURES = {
     'eagcn_layer_packed_bytes': (C.c_size_t, [C.POINTER(Batch), C.POINTER(LayerParams)]),
     'eagcn_layer_fwd_scratch_bytes': (C.c_size_t, [C.POINTER(Batch), C.POINTER(LayerParams)]),
     'eagcn_layer_bwd_scratch_bytes': (C.c_size_t, [C.POINTER(Batch), C.POINTER(LayerParams)]),
+    'eagcn_layer_route': (C.c_int, [C.POINTER(Batch), C.POINTER(LayerParams), C.POINTER(LayerBufs), C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.POINTER(C.c_int32 * 16)]),
     'eagcn_index_build': (C.c_int, [_fp, C.POINTER(_fp), C.POINTER(Batch), _fp, _fp]),
     'eagcn_index_from_bonds': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int64, C.POINTER(Batch), _fp, _fp]),
     'eagcn_index_rows': (C.c_int, [C.POINTER(Batch), _fp]),
@@ -326,7 +328,7 @@ class EagcnHipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 7    # include/eagcn_hip.h eagcn_abi_version(): struct layouts + signatures this binding was written against
+ABI_VERSION = 8    # include/eagcn_hip.h eagcn_abi_version(): struct layouts + signatures this binding was written against
 
 
 def load():

@@ -280,15 +280,10 @@ static GatArgs gat_args(const eagcn_batch* b, const eagcn_gat_params* p, const f
     GatArgs a;
     memset(&a, 0, sizeof(a));
     a.bt = *b; a.F = p->F; a.Fp = pad16(p->F); a.h = h; a.a = p->a; a.s12 = s12; a.alpha = p->alpha;
-    a.att_drop = (p->training && p->att_dropout > 0.0f) ? 1 : 0;
-    a.att_thr = (uint32_t)std::min(4294967295.0, (double)p->att_dropout * 4294967296.0);
-    a.att_inv = 1.0f / (1.0f - p->att_dropout);
-    a.att_seed_ = p->seed ^ GAT_ATT_STREAM;
-    a.do_drop = (p->training && p->dropout > 0.0f) ? 1 : 0;
-    a.thr = (uint32_t)std::min(4294967295.0, (double)p->dropout * 4294967296.0);
-    a.inv_keep = 1.0f / (1.0f - p->dropout);
-    a.seed_ = p->seed;
-    a.seed_dev = p->seed_dev;
+    const DropArgs ad = drop_args(p->att_dropout, p->training != 0, p->seed ^ GAT_ATT_STREAM, p->seed_dev);
+    const DropArgs od = drop_args(p->dropout, p->training != 0, p->seed, p->seed_dev);
+    a.att_drop = ad.on; a.att_thr = ad.thr; a.att_inv = ad.inv_keep; a.att_seed_ = ad.seed;
+    a.do_drop = od.on; a.thr = od.thr; a.inv_keep = od.inv_keep; a.seed_ = od.seed; a.seed_dev = od.seed_dev;
     return a;
 }
 static inline int row_grid(int T) { return std::max(1, std::min(cdiv(std::max(T, 1), 16), 2048)); }

@@ -244,12 +244,6 @@ static bool hidden_planes_only(const eagcn_batch* b, const eagcn_model* m, const
     return l + 1 < m->n_layers && sv.L[l].xout_planes && layer_reads_planes_only(b, &m->layer[l + 1], m->aux_stream != nullptr);
 }
 
-static void fill_drop(float p, int training, int* do_drop, uint32_t* thr, float* inv_keep) {
-    *do_drop = (training && p > 0.0f) ? 1 : 0;
-    *thr = (uint32_t)std::min(4294967295.0, (double)p * 4294967296.0);
-    *inv_keep = 1.0f / (1.0f - p);
-}
-
 }  // namespace eagcn
 
 using namespace eagcn;
@@ -313,12 +307,7 @@ static HeadPlan head_plan(const eagcn_batch* b, const eagcn_model* m, const Mode
     P.sync = m->stats_hook && m->training;
     // replicas of the forward sums (one with sync-BatchNorm: the hook all-reduces the first block in place)
     const int copies = P.sync ? 1 : HEAD_COPIES;
-    HeadDrop nodrop{0, 0u, 1.0f, 0, nullptr}, drop1 = nodrop;
-    {
-        int on; uint32_t thr; float inv_keep;
-        fill_drop(h->dropout, m->training, &on, &thr, &inv_keep);
-        drop1 = HeadDrop{on, thr, inv_keep, m->head_seed, m->head_seed_dev};
-    }
+    const HeadDrop nodrop{0, 0u, 1.0f, 0, nullptr}, drop1 = drop_args(h->dropout, m->training != 0, m->head_seed, m->head_seed_dev);
     P.f1 = HeadFwd{B, F, n1, sv.g, P.st_g, h->gbn_w, h->gbn_b, h->gbn_rm, h->gbn_rv, sv.bn_g, h->den1_w, sv.h1, nullptr, P.st_1,
                    m->training, 0, h->bn_eps, h->bn_momentum, nodrop};
     P.f2 = HeadFwd{B, n1, n2, sv.h1, P.st_1, h->bn1_w, h->bn1_b, h->bn1_rm, h->bn1_rv, sv.bn_1, h->den2_w, sv.h2, graph_rep, P.st_2,
@@ -425,8 +414,8 @@ static int model_forward_trunk(const eagcn_batch* b, const eagcn_model* m, const
         // relu / dropout / mask of the top layer applied while the atoms are summed; Graph_BN's column sums in the same launch
         ReadoutBn rb;
         rb.Y = LL.Y; rb.ldy = LL.fp; rb.bn = LL.bn; rb.fp = LL.fp;
-        fill_drop(last->dropout, last->training, &rb.do_drop, &rb.thr, &rb.inv_keep);
-        rb.seed = last->seed; rb.seed_dev = last->seed_dev;
+        const DropArgs ld = drop_args(last->dropout, last->training != 0, last->seed, last->seed_dev);
+        rb.do_drop = ld.on; rb.thr = ld.thr; rb.inv_keep = ld.inv_keep; rb.seed = ld.seed; rb.seed_dev = ld.seed_dev;
         rb.size = size; rb.mode = m->molfp_mode; rb.g = sv.g; rb.F = F; rb.st = st_g;
         rb.cnt0 = st_g + 2 * F; rb.cnt1 = st_1 + 2 * n1; rb.cnt2 = st_2 + 2 * n2;
         rb.st_copies = copies; rb.st_stride = sc.n_hst;
@@ -736,9 +725,12 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
         const float* dpad = (weighted && top) ? sc.dpad : nullptr;
         // (a layer that has only its edge-gradient reduction left hands it to the next layer's first kernel -- if one follows in
         //  this call)
-        RC(layer_backward_impl(b, &m->layer[l], &w, top ? nullptr : cur, top ? &rgd : nullptr, dpad,
-                               l > 0 ? other : dx0, input_only ? nullptr : &lg[l], stream, top && sampled, top ? &zb : nullptr,
-                               pend_in.eacc ? &pend_in : nullptr, (l > layer_lo && !input_only) ? &pend_out : nullptr, input_only));
+        LayerBwdOpts o;
+        o.rg = top ? &rgd : nullptr; o.dpad_views = top && sampled; o.zero_after = top ? &zb : nullptr;
+        o.drain_in = pend_in.eacc ? &pend_in : nullptr; o.drain_out = (l > layer_lo && !input_only) ? &pend_out : nullptr;
+        o.input_only = input_only;
+        RC(layer_backward_impl(b, &m->layer[l], &w, top ? nullptr : cur, dpad, l > 0 ? other : dx0, input_only ? nullptr : &lg[l],
+                               stream, o));
         pend_in = pend_out;
         if (l == layer_lo) pend_in.eacc = nullptr;
     }

@@ -32,6 +32,16 @@ struct AggArgs {
     const float* w_aw = nullptr;                 // [Fp] the view weight per packed column (colp row CP_AVEW)
     int w_drop = 0; uint32_t w_thr = 0; float w_inv_keep = 1.0f; uint64_t w_seed = 0; const uint64_t* w_seed_dev = nullptr;
 };
+// dropout of an activation as the kernels draw it: keep where hash(seed, element) >= thr, scaled by inv_keep (seed_dev: the seed
+// read on the device instead).  The ONE place threshold and scale are derived from the probability
+struct DropArgs { int on; uint32_t thr; float inv_keep; uint64_t seed; const uint64_t* seed_dev; };
+inline DropArgs drop_args(float p, bool training, uint64_t seed, const uint64_t* seed_dev) {
+    const double thr = (double)p * 4294967296.0;
+    return DropArgs{(training && p > 0.0f) ? 1 : 0, (uint32_t)(thr < 4294967295.0 ? thr : 4294967295.0), 1.0f / (1.0f - p), seed, seed_dev};
+}
+inline void agg_set_drop(AggArgs& a, const DropArgs& d) {
+    a.w_drop = d.on; a.w_thr = d.thr; a.w_inv_keep = d.inv_keep; a.w_seed = d.seed; a.w_seed_dev = d.seed_dev;
+}
 int agg_grid_x(const eagcn_batch* b);
 bool agg_ksplit(const eagcn_batch* b);
 int launch_agg(AggArgs a, bool trans, hipStream_t s);
@@ -197,7 +207,7 @@ int launch_gemm3_pair(const GemmDesc& dx, const GemmDesc& dw, const DwScatter* s
 
 // ---- model head (head2.hip) -----------------------------------------------------------------------------------------------
 constexpr int HEAD_COPIES = 8;  // replicas of the head's forward BatchNorm sums (one with sync-BatchNorm: the hook reduces ONE block)
-struct HeadDrop { int on; uint32_t thr; float inv_keep; uint64_t seed; const uint64_t* seed_dev; };
+using HeadDrop = DropArgs;
 struct HeadFwd {                 // y = act(bn(x)) . W  (+ column sums of y)
     int B, K, N;
     const float* x; const double* st_in; const float *gamma, *beta; float *run_mean, *run_var; float* bn;
@@ -258,12 +268,18 @@ struct EdgeDrain {
     float* datt_w[EAGCN_MAX_VIEWS]; float* dself_r[EAGCN_MAX_VIEWS]; int channels[EAGCN_MAX_VIEWS];
     const float* rsig;           // [K] sigmoid(self_r) of the layer the gradients belong to
 };
-// dpad_views: dpad_row holds one gradient row per VIEW ([K][ld_out]: sampled dropout of the non-stored rows) instead of one
-int layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w,
-                        const float* dxout, const ReadoutGrad* rg, const float* dpad_row, float* dx,
-                        const eagcn_layer_grads* g, void* stream, bool dpad_views = false,
-                        const ZeroJob* zero_after = nullptr, const EdgeDrain* drain_in = nullptr, EdgeDrain* drain_out = nullptr,
-                        bool input_only = false);
+// the optional arguments of a layer's backward
+struct LayerBwdOpts {
+    const ReadoutGrad* rg = nullptr;         // the upstream gradient per molecule (dxout is null then)
+    bool dpad_views = false;                 // dpad_row holds one gradient row per VIEW ([K][ld_out]: sampled dropout of the non-stored rows)
+    const ZeroJob* zero_after = nullptr;
+    const EdgeDrain* drain_in = nullptr;     // pending edge reduction of the layer above
+    EdgeDrain* drain_out = nullptr;          // receives this layer's, if nothing else is left for its gradient unpacking
+    bool input_only = false;                 // (below)
+};
+int layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const float* dxout,
+                        const float* dpad_row, float* dx, const eagcn_layer_grads* g, void* stream,
+                        const LayerBwdOpts& o = LayerBwdOpts{});
 // model engine (head.hip): the backward of eagcn_model_backward_input with layer 0's d(input) left PACKED ([T][ld_in] inside the scratch
 // block, *dx0), and where the packed input lives inside `saved` (attr.hip)
 int model_backward_input_packed(const eagcn_batch* b, const eagcn_model* m, const int64_t* size, void* saved, size_t saved_bytes,
@@ -280,9 +296,8 @@ int model_input_slot(const eagcn_batch* b, const eagcn_model* m, void* saved, si
 // is not written): the model engine asks for it when layer_reads_planes_only() holds for the layer above
 int layer_forward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, void* stream,
                        bool prepacked, bool skip_apply = false, bool planes_only = false);
-// true when BOTH directions of layer p take their input x from its bf16 plane images and never from the fp32 matrix (forward
-// product and the dX / dW pair on gemm_bx3.hip: the same conditions layer_forward_impl / layer_backward_impl test); a layer that
-// is then handed w->x == nullptr fails loudly if it reaches a fallback
+// true when BOTH directions of layer p take their input x from its bf16 plane images and never from the fp32 matrix (the route
+// layer.hip plans for a call that brings the planes); a layer that is then handed w->x == nullptr fails loudly if it reaches a fallback
 bool layer_reads_planes_only(const eagcn_batch* b, const eagcn_layer_params* p, bool aux_stream);
 // relu / dropout / mask / view merge of a layer from its saved Y and BatchNorm table (what layer_forward_impl ends with)
 int layer_apply_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, void* stream);

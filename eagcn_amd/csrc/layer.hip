@@ -790,6 +790,9 @@ struct LayerDims {
     int np;                      // 3 / 1: this layer's products run from bf16 operand planes (gemm_bx3.hip); 0: fp32 operands
     int bx_splits;               // ... and its weight gradient leaves as this many k-chunk slabs
 };
+// the forward aggregation of this batch runs on the LDS-staged kernel (lagg.hip; one BatchNorm slab per row block): asked by
+// layer_dims for the slab capacity and by plan_layer for the kernel
+static bool fwd_agg_lagg(const eagcn_batch* b, const ViewCols& vc) { return lagg_use(b, 0, false, &vc); }
 static LayerDims layer_dims(const eagcn_batch* b, const eagcn_layer_params* p) {
     LayerDims d;
     d.vc = view_cols(p);
@@ -798,7 +801,7 @@ static LayerDims layer_dims(const eagcn_batch* b, const eagcn_layer_params* p) {
     d.fin = layout_width(&p->in);
     d.ldo = p->structure == EAGCN_STRUCT_CONCATE ? d.fp : pad16(p->width[0]);
     d.gx = agg_grid_x(b);
-    d.gslab = std::max(d.gx, lagg_use(b, 0, false, &d.vc) ? lagg_slabs(b) : 0);
+    d.gslab = std::max(d.gx, fwd_agg_lagg(b, d.vc) ? lagg_slabs(b) : 0);
     // row-partial slabs of the BatchNorm backward: 7 rows per workgroup, at most 2048 workgroups and at most
     // 32 MB of fp64 partials (wide layers: Fp = 6320 -> 331 workgroups).  Fewer, longer workgroups were measured
     // slower (the kernel is bound by its instruction stream and one memory round trip per 7-row batch, not by the
@@ -823,20 +826,8 @@ static LayerDims layer_dims(const eagcn_batch* b, const eagcn_layer_params* p) {
     return d;
 }
 
-// Which layers run their products on the wave-autonomous balanced kernel (gemm3.hip): the hidden layers.  The first
-// layer (24 atom features) is a different animal: its forward product has two k-steps per tile and its weight gradient
-// seven 64x64 tiles with thousands of k-steps each -- a balanced cut would make every wave hand a partial tile to a
-// single owner per tile (measured: 0.2 ms instead of 0.02 ms) -- it stays on the workgroup-tiled kernels (gemm.hip).
-static bool gemm3_layer(int ld_in) {
-    static const bool on = [] { const char* v = getenv("EAGCN_NO_GEMM3"); return !(v && v[0] == '1'); }();
-    return on && ld_in >= 128 && gemm_mode() != 2;       // (the bf16 mode runs on the LDS-tiled kernels of gemm.hip)
-}
-
 struct Packed { float *Wcat, *WcatT, *colp, *sig, *rsig; uint16_t *Wp, *WTp; };   // Wp / WTp: [np][ld_in * fp] operand planes
-struct FwdScratch { void* gws; double* eacc; float *Wcat, *WcatT, *colp, *sig, *rsig; uint16_t *Wp, *WTp; double* stats; double* gsum;
-                    uint16_t* xp; };           // xp: planes of x when the caller did not bring them (layer-level path)
-static size_t carve_packed(void* base, const LayerDims& d, Packed* s) {
-    Carver c(base);
+static Packed take_packed(Carver& c, const LayerDims& d) {
     Packed t;
     t.Wcat = c.take<float>(d.wslab);
     t.WcatT = c.take<float>(d.wslab);
@@ -845,60 +836,57 @@ static size_t carve_packed(void* base, const LayerDims& d, Packed* s) {
     t.rsig = c.take<float>(EAGCN_MAX_VIEWS);
     t.Wp = c.take<uint16_t>(d.np ? (size_t)d.np * d.wpslab : 1);
     t.WTp = c.take<uint16_t>(d.np ? (size_t)d.np * d.wtpslab : 1);
+    return t;
+}
+static size_t carve_packed(void* base, const LayerDims& d, Packed* s) {
+    Carver c(base);
+    const Packed t = take_packed(c, d);
     if (s) *s = t;
     return c.off;
 }
-struct BwdScratch {
-    void* gws;                   // GEMM hand-off workspace: FIRST in both carvings, so that every layer of a model and both
-                                 // directions share one region (one flag clear per API call, kernels.h gemm3_clear_flags)
+// The scratch block of a forward (stats) or a backward (dY .. datt, dPp) call.  Both carvings start alike:
+struct LayerScratch {
+    void* gws;                   // GEMM hand-off workspace: FIRST, so that every layer of a model and both directions share one
+                                 // region (one flag clear per API call, kernels.h gemm3_clear_flags)
     double* eacc;                // edge-gradient accumulator slabs (kernels.h EDGE_COPIES): right behind it, zero between uses
-    float *Wcat, *WcatT, *colp, *sig, *rsig, *dY, *dP, *cc, *dWcat;
-    uint16_t *Wp, *WTp;
+    Packed pk;                   // the packed parameters -- or the caller's block (eagcn_layer_bufs.packed)
+    double* stats;
+    float *dY, *dP, *cc, *dWcat;
     double *slab, *slab_da, *datt, *gsum;
     uint16_t *dPp, *xp;          // planes of dP (written by the transposed aggregation) and of x when the caller did not bring them
 };
-static size_t carve_fwd(void* base, const eagcn_batch* b, const LayerDims& d, FwdScratch* s) {
+static size_t carve_layer(void* base, const eagcn_batch* b, const LayerDims& d, bool bwd, LayerScratch* s) {
     Carver c(base);
-    FwdScratch t;
+    LayerScratch t{};
     t.gws = c.take<char>(gemm3_workspace_bytes());
-    t.eacc = (double*)c.take<char>(edge_acc_bytes());        // (same place in both carvings: kernels.h EDGE_COPIES)
-    t.Wcat = c.take<float>(d.wslab);
-    t.WcatT = c.take<float>(d.wslab);
-    t.colp = c.take<float>((size_t)CP_ROWS * d.fp);
-    t.sig = c.take<float>(EAGCN_MAX_VIEWS * 256);
-    t.rsig = c.take<float>(EAGCN_MAX_VIEWS);
-    t.Wp = c.take<uint16_t>(d.np ? (size_t)d.np * d.wpslab : 1);
-    t.WTp = c.take<uint16_t>(d.np ? (size_t)d.np * d.wtpslab : 1);
-    t.stats = c.take<double>((size_t)d.gslab * d.fp * 2);
+    t.eacc = (double*)c.take<char>(edge_acc_bytes());
+    t.pk = take_packed(c, d);
+    if (!bwd) t.stats = c.take<double>((size_t)d.gslab * d.fp * 2);
+    else {
+        t.dY = c.take<float>((size_t)std::max(b->T, 1) * d.fp);
+        t.dP = c.take<float>((size_t)std::max(b->T, 1) * d.fp);
+        t.cc = c.take<float>((size_t)2 * d.fp);
+        t.dWcat = c.take<float>(d.wslab * std::max(std::max(d.nsplit, G3_XSEG), d.np ? d.bx_splits : 1));
+        t.slab = c.take<double>((size_t)d.gxb * d.fp * 2);
+        t.slab_da = c.take<double>((size_t)d.gxb * cdiv(d.fp, 1024) * EAGCN_MAX_VIEWS);
+        t.datt = c.take<double>((size_t)edge_grid_x(b) * EAGCN_MAX_VIEWS * EDGE_SLAB);
+    }
     t.gsum = c.take<double>((size_t)2 * d.fp + 8);
+    if (bwd) t.dPp = c.take<uint16_t>(d.np ? (size_t)d.np * bx_plane_elems(b->T, d.fp) : 1);
     t.xp = c.take<uint16_t>(d.np ? (size_t)d.np * bx_plane_elems(b->T, d.ld_in) : 1);
     if (s) *s = t;
     return c.off;
 }
-static size_t carve_bwd(void* base, const eagcn_batch* b, const LayerDims& d, BwdScratch* s) {
-    Carver c(base);
-    BwdScratch t;
-    t.gws = c.take<char>(gemm3_workspace_bytes());
-    t.eacc = (double*)c.take<char>(edge_acc_bytes());
-    t.Wcat = c.take<float>(d.wslab);
-    t.WcatT = c.take<float>(d.wslab);
-    t.colp = c.take<float>((size_t)CP_ROWS * d.fp);
-    t.sig = c.take<float>(EAGCN_MAX_VIEWS * 256);
-    t.rsig = c.take<float>(EAGCN_MAX_VIEWS);
-    t.Wp = c.take<uint16_t>(d.np ? (size_t)d.np * d.wpslab : 1);
-    t.WTp = c.take<uint16_t>(d.np ? (size_t)d.np * d.wtpslab : 1);
-    t.dY = c.take<float>((size_t)std::max(b->T, 1) * d.fp);
-    t.dP = c.take<float>((size_t)std::max(b->T, 1) * d.fp);
-    t.cc = c.take<float>((size_t)2 * d.fp);
-    t.dWcat = c.take<float>(d.wslab * std::max(std::max(d.nsplit, G3_XSEG), d.np ? d.bx_splits : 1));
-    t.slab = c.take<double>((size_t)d.gxb * d.fp * 2);
-    t.slab_da = c.take<double>((size_t)d.gxb * cdiv(d.fp, 1024) * EAGCN_MAX_VIEWS);
-    t.datt = c.take<double>((size_t)edge_grid_x(b) * EAGCN_MAX_VIEWS * EDGE_SLAB);
-    t.gsum = c.take<double>((size_t)2 * d.fp + 8);
-    t.dPp = c.take<uint16_t>(d.np ? (size_t)d.np * bx_plane_elems(b->T, d.fp) : 1);
-    t.xp = c.take<uint16_t>(d.np ? (size_t)d.np * bx_plane_elems(b->T, d.ld_in) : 1);
-    if (s) *s = t;
-    return c.off;
+// ... checked against the caller's block; the parameters an earlier call re-laid and the caller kept take the place of its own copy
+static int carve_checked(const eagcn_batch* b, const eagcn_layer_bufs* w, const LayerDims& d, bool bwd, LayerScratch* sc, const char* who) {
+    const size_t need = carve_layer(w->scratch, b, d, bwd, sc);
+    const size_t pneed = w->packed ? carve_packed(w->packed, d, &sc->pk) : 0;
+    if (need > w->scratch_bytes || pneed > w->packed_bytes) {
+        if (need > w->scratch_bytes) set_error("%s: scratch too small (%zu < %zu)", who, w->scratch_bytes, need);
+        else set_error("%s: packed buffer too small (%zu < %zu)", who, w->packed_bytes, pneed);
+        return EAGCN_ERR_SCRATCH;
+    }
+    return EAGCN_OK;
 }
 
 static int check_layer(const eagcn_batch* b, const eagcn_layer_params* p, const char* who) {
@@ -943,11 +931,211 @@ static ParamPtrs param_ptrs(const eagcn_batch* b, const eagcn_layer_params* p) {
 
 static inline int ew_grid(size_t n) { return (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 2048)); }
 
-}  // namespace eagcn
+static void launch_pack_params(const ParamPtrs& pp, const LayerDims& d, const ColMapD& in, const Packed& pk, hipStream_t s) {
+    ProfScope ps(PROF_PACK, s);
+    pack_params_kernel<<<ew_grid(d.wslab), 256, 0, s>>>(pp, d.vc, in, d.ld_in, d.fp, pk.Wcat, pk.WcatT, pk.colp, pk.sig, pk.rsig,
+                                                        BxOut{d.np ? pk.Wp : nullptr, d.wpslab, d.np, d.ld_in},
+                                                        BxOut{d.np ? pk.WTp : nullptr, d.wtpslab, d.np, d.fp});
+}
+// algorithmic flops of the flat transform: exact widths, packed rows
+static double layer_gemm_work(const eagcn_batch* b, const eagcn_layer_params* p, const LayerDims& d) {
+    double fsum = 0.0;
+    for (int k = 0; k < p->K; ++k) fsum += p->width[k];
+    return 2.0 * (double)b->T * (double)d.fin * fsum;
+}
 
-static int apply_launch_(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const eagcn::LayerDims& d,
-                         const float* colp, hipStream_t s, bool planes_only = false);
-#define apply_launch apply_launch_
+// ---- the three products of a layer: P = X.W^T, dX = dP.W^T, dW = X^T.dP ---------------------------------------------------------
+// ONE description of each, for the executors below and for plan_layer (which only asks whether a kernel takes them).
+struct LayerOperands {
+    const float* x; const uint16_t* xp;               // the input: fp32, and its planes (the caller's, or the scratch block's copy)
+    float* P; Packed pk;
+    float* dP; uint16_t* dPp; float* dx; float* dWcat;
+};
+static LayerOperands layer_operands(const eagcn_layer_bufs* w, const LayerScratch& sc, float* dx) {
+    return LayerOperands{w->x, w->x_planes ? w->x_planes : sc.xp, w->P, sc.pk, sc.dP, sc.dPp, dx, sc.dWcat};
+}
+// ... from bf16 operand planes (gemm_bx3.hip): dX and dW share one persistent launch, dW leaves as k-chunk slabs (summed by
+// unpack_grads), dP comes from the transposed aggregation as planes and is never written as fp32
+struct PlaneProducts { BxProb bp, bx, bw; };
+static PlaneProducts layer_plane_products(const eagcn_batch* b, const LayerDims& d, const LayerOperands& o) {
+    const size_t xstride = bx_plane_elems(b->T, d.ld_in), pstride = bx_plane_elems(b->T, d.fp);
+    const int* T_dev = b->meta + EAGCN_META_T;
+    PlaneProducts q;
+    memset(&q, 0, sizeof(q));
+    q.bp.A = BxPlanes{o.xp, xstride, d.ld_in, b->T}; q.bp.B = BxPlanes{o.pk.WTp, d.wtpslab, d.ld_in, d.fp}; q.bp.C = o.P; q.bp.ldc = d.fp;
+    q.bp.M = b->T; q.bp.N = d.fp; q.bp.K = d.ld_in; q.bp.M_dev = T_dev; q.bp.tn = 0; q.bp.splits = 1;
+    q.bx.A = BxPlanes{o.dPp, pstride, d.fp, b->T}; q.bx.B = BxPlanes{o.pk.Wp, d.wpslab, d.fp, d.ld_in}; q.bx.C = o.dx; q.bx.ldc = d.ld_in;
+    q.bx.M = b->T; q.bx.N = d.ld_in; q.bx.K = d.fp; q.bx.M_dev = T_dev; q.bx.tn = 0; q.bx.splits = 1;
+    q.bw.A = BxPlanes{o.xp, xstride, d.ld_in, b->T}; q.bw.B = BxPlanes{o.dPp, pstride, d.fp, b->T};
+    q.bw.C = o.dWcat; q.bw.ldc = d.fp; q.bw.M = d.ld_in; q.bw.N = d.fp; q.bw.K = b->T; q.bw.K_dev = T_dev; q.bw.tn = 1;
+    q.bw.splits = d.bx_splits; q.bw.slab = d.wslab;
+    return q;
+}
+// ... from fp32 operands: gp = the forward on the pre-transposed weight (NT form: gemm3.hip), gt = the same on Wcat (gemm.hip)
+struct Fp32Products { GemmDesc gp, gt, gx, gw; };
+static Fp32Products layer_fp32_products(const eagcn_batch* b, const LayerDims& d, const LayerOperands& o, double work) {
+    const int* T_dev = b->meta + EAGCN_META_T;
+    Fp32Products q{GemmDesc{0, 1, b->T, d.fp, d.ld_in, o.x, d.ld_in, o.pk.WcatT, d.ld_in, o.P, d.fp, 1, 0, work},
+                   GemmDesc{0, 0, b->T, d.fp, d.ld_in, o.x, d.ld_in, o.pk.Wcat, d.fp, o.P, d.fp, 1, 0, work},
+                   GemmDesc{0, 1, b->T, d.ld_in, d.fp, o.dP, d.fp, o.pk.Wcat, d.fp, o.dx, d.ld_in, 1, 0, work},
+                   GemmDesc{1, 0, d.ld_in, d.fp, b->T, o.x, d.ld_in, o.dP, d.fp, o.dWcat, d.fp, d.nsplit, d.wslab, work}};
+    q.gp.M_dev = T_dev; q.gt.M_dev = T_dev; q.gx.M_dev = T_dev; q.gw.K_dev = T_dev;
+    return q;
+}
+
+// ---- the route of a layer call -----------------------------------------------------------------------------------------------------
+// Which kernels a layer runs for a batch is decided ONCE per call, by plan_layer: a pure host function of the batch description,
+// the layer, the buffers' addresses (alignment only: nothing is dereferenced) and the switches below.  layer_forward_impl and
+// layer_backward_impl carry the route out; eagcn_layer_route shows it to the tests.  (The values are part of the C ABI:
+// include/eagcn_hip.h.)
+// REFUSED: x exists as plane images only and the plane products do not apply -- the call fails
+enum FwdProd { FWD_NONE = 0, FWD_PLANES, FWD_BALANCED, FWD_TILED, FWD_REFUSED };        // gemm_bx3.hip | gemm3.hip | gemm.hip
+enum AggPath { AGG_DENSE = 0, AGG_LAGG };                                 // matrix-core kernels of agg.hip | LDS-staged bond lists (lagg.hip)
+// where the BatchNorm backward's second pass dY' = sc (dH - c1 - xhat c2) happens
+enum Bn2 {
+    BN2_NONE = 0,
+    BN2_ELEMENTWISE,             // bn_bwd_apply_kernel on the dH the first pass stored (Concate: the upstream gradient is as wide as dH)
+    BN2_REDUCE_APPLY,            // bn_bwd_reduce_kernel again, dH re-formed (Weighted_sum: the upstream gradient is K times narrower:
+                                 // no write and read of T x Fp floats, HIV 9.74 -> 9.53 ms per step)
+    BN2_STAGED_FROM_DH,          // lagg.hip, while it stages the rows of the stored dH (it is the only consumer of dY')
+    BN2_STAGED_FROM_UPSTREAM,    // lagg.hip re-forms dH AND dY' from the layer's upstream gradient: neither exists in memory
+    BN2_STAGED_ROWMASK           // ... of a Concate layer in eval mode (input-only form: dH = upstream x row mask x relu')
+};
+enum EdgePath { EDGE_NONE = 0, EDGE_WITH_LAGG, EDGE_COLAUNCH, EDGE_SEPARATE };   // lagg.hip's gathers | one grid with agg.hip | own launch
+enum BwdProd {
+    BWD_NONE = 0, BWD_PLANES_PAIR, BWD_PLANES_DW, BWD_PLANES_DX,      // gemm_bx3.hip: dX with dW | dW alone | dX alone (input-only)
+    BWD_G3_XK, BWD_G3_SCATTER,   // gemm3.hip pair: dW as one partial slab per XCD | written straight into the per-view gradients
+    BWD_TILED_PAIR, BWD_TILED_SEPARATE, BWD_TILED_DX,                 // gemm.hip: one grid | dW on the side stream, then dX | dX alone
+    BWD_REFUSED
+};
+struct PlanAsk {
+    bool has_dx;                 // d(layer input) is asked for
+    bool mol_grad;               // the upstream gradient comes per molecule (ReadoutGrad)
+    bool input_only;
+    bool has_drain_out;          // a layer below could take this layer's edge-gradient reduction
+};
+struct LayerRoute {
+    FwdProd fwd_prod = FWD_NONE; bool fwd_split_x = false;      // split: the planes of x are produced here (launch_bx3_split)
+    AggPath fwd_agg = AGG_DENSE, bwd_agg = AGG_DENSE;
+    Bn2 bn2 = BN2_NONE;
+    bool rows_first = false, rows_late = false;                  // launch_readout_bwd_rows before the reduction | before the aggregation
+    bool store_dh = false;                                       // the first pass of the BatchNorm backward stores dH
+    EdgePath edge = EDGE_NONE; bool edge_atomic = false;         // atomic: the partials leave through the shared accumulators
+    BwdProd bwd_prod = BWD_NONE; bool bwd_split_x = false;
+    bool defer_drain = false;                                    // the edge reduction is left to the next layer's first kernel
+    bool bn2_staged() const { return bn2 >= BN2_STAGED_FROM_DH; }
+    bool bwd_planes() const { return bwd_prod >= BWD_PLANES_PAIR && bwd_prod <= BWD_PLANES_DX; }
+};
+
+// the switches (each read once).  EAGCN_AGG / EAGCN_LAGG_*: lagg.hip; EAGCN_GEMM_X6: gemm.hip; EAGCN_GEMM3_XK: gemm3.hip
+static bool env_is(const char* name, char c) { const char* v = getenv(name); return v && v[0] == c; }
+#define EAGCN_SWITCH(fn, expr) static bool fn() { static const bool on = (expr); return on; }
+EAGCN_SWITCH(sw_gemm3, !env_is("EAGCN_NO_GEMM3", '1'))
+EAGCN_SWITCH(sw_planes_only, !env_is("EAGCN_PLANES_ONLY", '0'))
+EAGCN_SWITCH(sw_lagg_fuses_bn, !env_is("EAGCN_LAGG_FUSE_BN", '0'))        // 0: lagg.hip never absorbs the BatchNorm backward's second pass
+EAGCN_SWITCH(sw_edge_atomic, !env_is("EAGCN_EDGE_SLABS", '1'))
+EAGCN_SWITCH(sw_rows_first, !env_is("EAGCN_W_ROWS_FIRST", '0'))
+EAGCN_SWITCH(sw_colaunch, !env_is("EAGCN_NO_COLAUNCH", '1'))
+EAGCN_SWITCH(sw_pair, !env_is("EAGCN_NO_PAIR", '1'))
+EAGCN_SWITCH(sw_edge_defer, !env_is("EAGCN_NO_EDGE_DEFER", '1'))
+#undef EAGCN_SWITCH
+// EAGCN_BWD_STORE_DH=1 / 0 forces the elementwise / the re-forming second pass (default: Bn2 above)
+static bool bn_bwd_two_pass(bool weighted) {
+    static const int force = [] { const char* v = getenv("EAGCN_BWD_STORE_DH"); return v ? (v[0] == '1' ? 1 : 0) : -1; }();
+    return force < 0 ? weighted : force == 0;
+}
+static int bn_apply_map() {
+    static const int v = [] { const char* e = getenv("EAGCN_BN_APPLY_MAP"); return e ? atoi(e) : -1; }();
+    return v;
+}
+// Which layers run their products on the wave-autonomous balanced kernel (gemm3.hip): the hidden layers.  The first
+// layer (24 atom features) is a different animal: its forward product has two k-steps per tile and its weight gradient
+// seven 64x64 tiles with thousands of k-steps each -- a balanced cut would make every wave hand a partial tile to a
+// single owner per tile (measured: 0.2 ms instead of 0.02 ms) -- it stays on the workgroup-tiled kernels (gemm.hip).
+static bool gemm3_layer(int ld_in) {
+    return sw_gemm3() && ld_in >= 128 && gemm_mode() != 2;       // (the bf16 mode runs on the LDS-tiled kernels of gemm.hip)
+}
+
+static LayerRoute plan_layer(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const LayerDims& d,
+                             PlanAsk ask) {
+    LayerRoute r;
+    const bool wt = p->structure == EAGCN_STRUCT_WEIGHTED, forked = w->aux_stream != nullptr;
+    bool general = false;                             // (code books: the edge reduction reads a view's whole histogram per channel)
+    for (int k = 0; k < p->K; ++k) general = general || b->rel_vec[k] != nullptr;
+    r.edge_atomic = sw_edge_atomic() && !general;
+    r.store_dh = !bn_bwd_two_pass(wt);
+    if (b->T <= 0) return r;                          // no packed row: no product, no aggregation, a row-less reduction
+    r.fwd_agg = fwd_agg_lagg(b, d.vc) ? AGG_LAGG : AGG_DENSE;
+    float* const some_dx = reinterpret_cast<float*>(static_cast<uintptr_t>(4096));       // (the products' checks want an address)
+    // (addresses enter through their alignment alone and every piece of either carving is 256-byte aligned: the backward's stands for both)
+    LayerScratch sc;
+    carve_layer(w->scratch, b, d, true, &sc);
+    if (w->packed) carve_packed(w->packed, d, &sc.pk);
+    const LayerOperands o = layer_operands(w, sc, ask.has_dx ? some_dx : nullptr);
+    const PlaneProducts bq = layer_plane_products(b, d, o);
+    const Fp32Products gq = layer_fp32_products(b, d, o, 0.0);
+
+    // forward product: planes (x planes from the layer below, or split here), else the balanced kernel on the pre-transposed
+    // weight; operands that are not 16-byte aligned fall back to the workgroup-tiled kernel
+    r.fwd_split_x = d.np && !w->x_planes;
+    if (d.np && bx3_ok(bq.bp)) r.fwd_prod = FWD_PLANES;
+    else if (!w->x) r.fwd_prod = FWD_REFUSED;
+    else r.fwd_prod = (gemm3_layer(d.ld_in) && gemm3_ok(gq.gp)) ? FWD_BALANCED : FWD_TILED;
+
+    // The LDS-staged kernel runs the transposed aggregation + edge gradients (which must then leave through the shared
+    // accumulators).  It absorbs the second pass of the BatchNorm backward: of a Concate layer from the stored dH, of a Weighted_sum
+    // layer from the upstream gradient; input-only: no edge gradients to route, and the staging absorbs whatever the structure
+    const bool fuse_w = bn_bwd_two_pass(wt) && wt && sw_lagg_fuses_bn() && lagg_wfuse();
+    const bool absorbs = sw_lagg_fuses_bn() && (!bn_bwd_two_pass(wt) || (wt && lagg_wfuse()));
+    const bool lagg = ask.input_only ? lagg_use(b, 1, true) : (r.edge_atomic && lagg_use(b, 1, absorbs));
+    r.bwd_agg = lagg ? AGG_LAGG : AGG_DENSE;
+    if (ask.input_only && !p->training) {
+        // eval-mode BatchNorm backward of the input-only form: dY' = sc dH (the running statistics are constants: c1 = c2 = 0), no
+        // reduction and no finalize; off the LDS-staged kernel the reduction kernel's second pass forms dY' from zero means
+        r.bn2 = !lagg ? BN2_REDUCE_APPLY : wt ? BN2_STAGED_FROM_UPSTREAM : BN2_STAGED_ROWMASK;
+        r.rows_first = lagg && ask.mol_grad;
+    } else if (lagg && fuse_w) {
+        // lagg.hip wants a per-molecule read-out gradient as ROWS ([T][ldo], K times narrower than dH) -- written first, so that the
+        // reduction reads them with 16-byte loads as well instead of gathering dg[molecule] element by element
+        r.bn2 = BN2_STAGED_FROM_UPSTREAM;
+        r.rows_first = ask.mol_grad && sw_rows_first();
+        r.rows_late = ask.mol_grad && !r.rows_first;
+    } else if (bn_bwd_two_pass(wt)) r.bn2 = BN2_REDUCE_APPLY;
+    else r.bn2 = (lagg && sw_lagg_fuses_bn()) ? BN2_STAGED_FROM_DH : BN2_ELEMENTWISE;
+
+    const bool planes = d.np && !forked && bx3_ok(bq.bw) && (!ask.has_dx || bx3_ok(bq.bx));
+    r.bwd_split_x = planes && !w->x_planes && !ask.input_only;
+    if (ask.input_only) r.bwd_prod = planes ? BWD_PLANES_DX : BWD_TILED_DX;
+    else if (!planes && !w->x) r.bwd_prod = BWD_REFUSED;
+    if (r.bwd_prod != BWD_NONE) return r;
+    r.edge = (lagg && r.edge_atomic) ? EDGE_WITH_LAGG : (!forked && sw_colaunch()) ? EDGE_COLAUNCH : EDGE_SEPARATE;
+    if (planes) r.bwd_prod = ask.has_dx ? BWD_PLANES_PAIR : BWD_PLANES_DW;
+    else if (!forked && ask.has_dx && gemm3_layer(d.ld_in) && gemm3_ok(gq.gw) && gemm3_ok(gq.gx))
+        r.bwd_prod = gemm3_xk_enabled() ? BWD_G3_XK : BWD_G3_SCATTER;
+    else r.bwd_prod = (ask.has_dx && !forked && sw_colaunch() && sw_pair()) ? BWD_TILED_PAIR : BWD_TILED_SEPARATE;
+    // nothing but the edge reduction is left for this layer (no dW slabs to sum): the next layer's first backward kernel does it
+    r.defer_drain = sw_edge_defer() && ask.has_drain_out && r.edge_atomic && r.bwd_prod == BWD_G3_SCATTER && !forked;
+    return r;
+}
+
+static int apply_launch(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const LayerDims& d,
+                        const float* colp, hipStream_t s, bool planes_only = false) {
+    ProfScope psbn(PROF_BN, s);
+    ApplyArgs aa;
+    aa.bt = *b; aa.vc = d.vc; aa.structure = p->structure; aa.fp = d.fp; aa.Y = w->Y; aa.ldy = d.fp;
+    aa.bn = w->bn; aa.colp = colp; aa.out = w->xout; aa.ldo = d.ldo; aa.pad_row = w->pad_row;
+    const DropArgs dr = drop_args(p->dropout, p->training != 0, p->seed, p->seed_dev);
+    aa.do_drop = dr.on; aa.thr = dr.thr; aa.inv_keep = dr.inv_keep; aa.seed = dr.seed; aa.seed_dev = dr.seed_dev;
+    aa.planes = BxOut{gemm_planes() ? w->xout_planes : nullptr, bx_plane_elems(b->T, d.ldo), gemm_planes(), b->T};
+    if (planes_only && aa.planes.p) aa.out = nullptr;        // (the only reader is the layer above, through the planes)
+    aa.tile_map = bn_apply_map() >= 0 ? bn_apply_map() : (aa.planes.p ? 1 : 0);
+    const size_t nthr = aa.tile_map ? (size_t)cdiv(std::max(b->T, 1), 8) * cdiv(d.ldo, 32) * 64 : (size_t)std::max(b->T, 1) * d.ldo / 4;
+    bn_apply_kernel<<<ew_grid(nthr), 256, 0, s>>>(aa);
+    EAGCN_LAUNCH_CHECK();
+    return EAGCN_OK;
+}
+
+}  // namespace eagcn
 
 using namespace eagcn;
 
@@ -957,26 +1145,38 @@ extern "C" int eagcn_layer_out_ld(const eagcn_layer_params* p) {
     return p->structure == EAGCN_STRUCT_CONCATE ? eagcn_layer_fp(p) : pad16(p->width[0]);
 }
 extern "C" size_t eagcn_layer_packed_bytes(const eagcn_batch* b, const eagcn_layer_params* p) {
-    LayerDims d = layer_dims(b, p);
-    return carve_packed(nullptr, d, nullptr);
+    return carve_packed(nullptr, layer_dims(b, p), nullptr);
 }
 extern "C" size_t eagcn_layer_fwd_scratch_bytes(const eagcn_batch* b, const eagcn_layer_params* p) {
-    LayerDims d = layer_dims(b, p);
-    return carve_fwd(nullptr, b, d, nullptr);
+    return carve_layer(nullptr, b, layer_dims(b, p), false, nullptr);
 }
 extern "C" size_t eagcn_layer_bwd_scratch_bytes(const eagcn_batch* b, const eagcn_layer_params* p) {
-    LayerDims d = layer_dims(b, p);
-    return carve_bwd(nullptr, b, d, nullptr);
+    return carve_layer(nullptr, b, layer_dims(b, p), true, nullptr);
 }
 
+extern "C" int eagcn_layer_route(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, int has_dx,
+                                 int mol_grad, int input_only, int has_drain_out, int32_t out[16]) {
+    int rc = check_layer(b, p, "eagcn_layer_route");
+    if (rc) return rc;
+    EAGCN_CHECK_ARG(w && out, "eagcn_layer_route: null argument");
+    const LayerRoute r = plan_layer(b, p, w, layer_dims(b, p), PlanAsk{has_dx != 0, mol_grad != 0, input_only != 0, has_drain_out != 0});
+    const int32_t v[16] = {(int32_t)r.fwd_prod, r.fwd_split_x, (int32_t)r.fwd_agg, (int32_t)r.bwd_agg, (int32_t)r.bn2, r.rows_first, r.rows_late, r.store_dh, (int32_t)r.edge,
+                           r.edge_atomic, (int32_t)r.bwd_prod, r.bwd_split_x, r.defer_drain,
+                           layer_reads_planes_only(b, p, w->aux_stream != nullptr), 0, 0};
+    memcpy(out, v, sizeof(v));
+    return EAGCN_OK;
+}
+
+// a layer-level call starts with the hand-off flags of its scratch block cleared (the model engine clears once per model call)
+static int clear_handoff_flags(const eagcn_layer_bufs* w, void* stream) {
+    if (!(w && w->scratch && w->scratch_bytes >= gemm3_workspace_bytes())) return EAGCN_OK;
+    return gemm3_clear_flags(w->scratch, w->scratch_bytes, (hipStream_t)stream);
+}
 extern "C" int eagcn_layer_forward(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w,
                                    void* stream) {
     EAGCN_CHECK_GEMM3("eagcn_layer_forward");
-    if (w && w->scratch && w->scratch_bytes >= gemm3_workspace_bytes()) {
-        int rc = gemm3_clear_flags(w->scratch, w->scratch_bytes, (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    return layer_forward_impl(b, p, w, stream, false);
+    const int rc = clear_handoff_flags(w, stream);
+    return rc ? rc : layer_forward_impl(b, p, w, stream, false);
 }
 
 // parameters of up to four layers re-laid into their `packed` blocks by ONE launch (model engine)
@@ -1013,6 +1213,10 @@ int eagcn::pack_params_all(const eagcn_batch* b, const eagcn_layer_params* const
     return EAGCN_OK;
 }
 
+// kernels templated by the number of partial slabs a thread sums at a time: few slabs -> 16 columns per workgroup, many -> 4
+#define EAGCN_BY_SLABS(n, kernel, ...) do { if ((n) > 64) kernel<64><<<cdiv(d.fp, 4), 256, 0, s>>>(__VA_ARGS__); \
+                                            else kernel<16><<<cdiv(d.fp, 16), 256, 0, s>>>(__VA_ARGS__); } while (0)
+
 int eagcn::layer_forward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w,
                               void* stream, bool prepacked, bool skip_apply, bool planes_only) {
     hipStream_t s = (hipStream_t)stream;
@@ -1023,131 +1227,82 @@ int eagcn::layer_forward_impl(const eagcn_batch* b, const eagcn_layer_params* p,
     EAGCN_CHECK_ARG(b->T == 0 || ((w->x || w->x_planes) && w->P && w->Y && w->rscale), "eagcn_layer_forward: null activation buffer");
     EAGCN_CHECK_ARG(!planes_only || (w->xout_planes && gemm_planes()), "eagcn_layer_forward: planes-only output without plane images");
     const LayerDims d = layer_dims(b, p);
-    FwdScratch sc;
-    const size_t need = carve_fwd(w->scratch, b, d, &sc);
-    if (need > w->scratch_bytes) {
-        set_error("eagcn_layer_forward: scratch too small (%zu < %zu)", w->scratch_bytes, need);
-        return EAGCN_ERR_SCRATCH;
-    }
+    LayerScratch sc;
+    rc = carve_checked(b, w, d, false, &sc, "eagcn_layer_forward");
+    if (rc) return rc;
     const ParamPtrs pp = param_ptrs(b, p);
-    const ColMapD in = make_colmap(&p->in);
-    if (w->packed) {
-        Packed pk;
-        const size_t pneed = carve_packed(w->packed, d, &pk);
-        if (pneed > w->packed_bytes) {
-            set_error("eagcn_layer_forward: packed buffer too small (%zu < %zu)", w->packed_bytes, pneed);
-            return EAGCN_ERR_SCRATCH;
-        }
-        sc.Wcat = pk.Wcat; sc.WcatT = pk.WcatT; sc.colp = pk.colp; sc.sig = pk.sig; sc.rsig = pk.rsig;
-        sc.Wp = pk.Wp; sc.WTp = pk.WTp;
-    }
     EAGCN_CHECK_ARG(!prepacked || w->packed, "eagcn_layer_forward: prepacked parameters need the packed block");
-    if (!prepacked) {
-        ProfScope ps(PROF_PACK, s);
-        pack_params_kernel<<<ew_grid(d.wslab), 256, 0, s>>>(pp, d.vc, in, d.ld_in, d.fp, sc.Wcat, sc.WcatT, sc.colp, sc.sig, sc.rsig,
-                                                            BxOut{d.np ? sc.Wp : nullptr, d.wpslab, d.np, d.ld_in},
-                                                            BxOut{d.np ? sc.WTp : nullptr, d.wtpslab, d.np, d.fp});
-    }
+    if (!prepacked) launch_pack_params(pp, d, make_colmap(&p->in), sc.pk, s);
     EAGCN_LAUNCH_CHECK();
-    // algorithmic flops of the flat transform: exact widths, packed rows
-    double fsum = 0.0;
-    for (int k = 0; k < p->K; ++k) fsum += p->width[k];
-    const double gemm_work = 2.0 * (double)b->T * (double)d.fin * fsum;
+    const LayerRoute r = plan_layer(b, p, w, d, PlanAsk{false, false, false, false});
     int nslab = 0, tiles_per_wg = agg_ksplit(b) ? 1 : 4;
     if (b->T > 0) {
-        // P = X.[W_1|..|W_K]: NT form on the pre-transposed weight (wave-autonomous balanced kernel, gemm3.hip); operands
-        // that are not 16-byte aligned fall back to the workgroup-tiled kernel
-        GemmDesc g3{0, 1, b->T, d.fp, d.ld_in, w->x, d.ld_in, sc.WcatT, d.ld_in, w->P, d.fp, 1, 0, gemm_work};
-        g3.M_dev = b->meta + EAGCN_META_T;
-        BxProb bp;
-        memset(&bp, 0, sizeof(bp));
-        if (d.np) {
-            // the same product from bf16 operand planes (gemm_bx3.hip): x planes from the layer below, or split here
-            const size_t xstride = bx_plane_elems(b->T, d.ld_in);
-            const uint16_t* xp = w->x_planes;
-            if (!xp) {
-                EAGCN_CHECK_ARG(w->x, "eagcn_layer_forward: neither an fp32 input nor its plane images");
-                rc = launch_bx3_split(w->x, b->T, b->meta + EAGCN_META_T, d.ld_in, sc.xp, xstride, b->T, d.np, s);
-                if (rc) return rc;
-                xp = sc.xp;
-            }
-            bp.A = BxPlanes{xp, xstride, d.ld_in, b->T}; bp.B = BxPlanes{sc.WTp, d.wtpslab, d.ld_in, d.fp}; bp.C = w->P; bp.ldc = d.fp;
-            bp.M = b->T; bp.N = d.fp; bp.K = d.ld_in; bp.M_dev = b->meta + EAGCN_META_T; bp.tn = 0; bp.splits = 1;
-        }
-        if (d.np && bx3_ok(bp)) {
-            rc = launch_bx3(bp, nullptr, d.np, s, gemm_work, PROF_GEMM, bx3_pick_wide(bp, nullptr, b->t_hint));
-        } else if (!w->x) {
+        const double gemm_work = layer_gemm_work(b, p, d);
+        const LayerOperands o = layer_operands(w, sc, nullptr);
+        const Fp32Products gq = layer_fp32_products(b, d, o, gemm_work);
+        if (r.fwd_prod == FWD_REFUSED) {
             set_error("eagcn_layer_forward: the input exists as plane images only and the plane product does not apply");
             return EAGCN_ERR_ARG;
-        } else if (gemm3_layer(d.ld_in) && gemm3_ok(g3)) {
-            rc = launch_gemm3(g3, nullptr, sc.gws, gemm3_workspace_bytes(), s);
-        } else {
-            GemmDesc g{0, 0, b->T, d.fp, d.ld_in, w->x, d.ld_in, sc.Wcat, d.fp, w->P, d.fp, 1, 0, gemm_work};
-            g.M_dev = b->meta + EAGCN_META_T;
-            rc = launch_gemm(g, s);
         }
-        if (rc) return rc;
-        {
-            AggArgs a;
-            a.bt = *b; a.vc = d.vc; a.src = w->P; a.lds = d.fp; a.dst = w->Y; a.ldd = d.fp;
-            a.sig = sc.sig; a.rsig = sc.rsig; a.rscale = w->rscale; a.stats = sc.stats; a.nchunk = 1;
-            if (lagg_use(b, 0, false, &d.vc)) {                // LDS-staged bond-list aggregation (lagg.hip): one slab per row block
-                rc = launch_lagg_fwd(a, s);
-                nslab = lagg_slabs(b);
-                tiles_per_wg = -1;
-            } else {
-                rc = launch_agg(a, false, s);
-                nslab = d.gx;
-            }
+        if (r.fwd_split_x) {
+            rc = launch_bx3_split(w->x, b->T, b->meta + EAGCN_META_T, d.ld_in, sc.xp, bx_plane_elems(b->T, d.ld_in), b->T, d.np, s);
             if (rc) return rc;
         }
+        switch (r.fwd_prod) {
+        case FWD_PLANES: {
+            const BxProb bp = layer_plane_products(b, d, o).bp;
+            rc = launch_bx3(bp, nullptr, d.np, s, gemm_work, PROF_GEMM, bx3_pick_wide(bp, nullptr, b->t_hint));
+            break;
+        }
+        case FWD_BALANCED: rc = launch_gemm3(gq.gp, nullptr, sc.gws, gemm3_workspace_bytes(), s); break;
+        default: rc = launch_gemm(gq.gt, s); break;
+        }
+        if (rc) return rc;
+        AggArgs a;
+        a.bt = *b; a.vc = d.vc; a.src = w->P; a.lds = d.fp; a.dst = w->Y; a.ldd = d.fp;
+        a.sig = sc.pk.sig; a.rsig = sc.pk.rsig; a.rscale = w->rscale; a.stats = sc.stats; a.nchunk = 1;
+        if (r.fwd_agg == AGG_LAGG) {                  // one slab per row block
+            rc = launch_lagg_fwd(a, s);
+            nslab = lagg_slabs(b);
+            tiles_per_wg = -1;
+        } else {
+            rc = launch_agg(a, false, s);
+            nslab = d.gx;
+        }
+        if (rc) return rc;
     }
     const double M = (double)b->B * (double)b->N;
     {
-    ProfScope psbn(PROF_BN, s);
-    if (w->stats_hook && p->training) {
-        // sync-BatchNorm: this rank's sums -> one vector, summed across the ranks by the caller's hook, finalize from that
-        if (nslab > 64) bn_stats_sum_kernel<64><<<cdiv(d.fp, 4), 256, 0, s>>>(sc.stats, nslab, d.fp, M, sc.gsum, b->meta, 1, tiles_per_wg, 0, b->B);
-        else bn_stats_sum_kernel<16><<<cdiv(d.fp, 16), 256, 0, s>>>(sc.stats, nslab, d.fp, M, sc.gsum, b->meta, 1, tiles_per_wg, 0, b->B);
-        EAGCN_LAUNCH_CHECK();
-        if (w->stats_hook(sc.gsum, 2 * d.fp + 1, stream, w->stats_user)) {
-            set_error("eagcn_layer_forward: the sync-BatchNorm all-reduce hook failed");
-            return EAGCN_ERR_HIP;
+        ProfScope psbn(PROF_BN, s);
+        const bool sync = w->stats_hook && p->training;
+        if (sync) {
+            // sync-BatchNorm: this rank's sums -> one vector, summed across the ranks by the caller's hook, finalize from that
+            EAGCN_BY_SLABS(nslab, bn_stats_sum_kernel, sc.stats, nslab, d.fp, M, sc.gsum, b->meta, 1, tiles_per_wg, 0, b->B);
+            EAGCN_LAUNCH_CHECK();
+            if (w->stats_hook(sc.gsum, 2 * d.fp + 1, stream, w->stats_user)) {
+                set_error("eagcn_layer_forward: the sync-BatchNorm all-reduce hook failed");
+                return EAGCN_ERR_HIP;
+            }
+            nslab = 1;
         }
-        bn_finalize_kernel<16><<<cdiv(d.fp, 16), 256, 0, s>>>(sc.gsum, 1, d.fp, M, p->training, p->bn_eps, p->bn_momentum, sc.colp,
-                                                                pp, d.vc, w->bn, b->meta, 0, b->B, sc.gsum + 2 * d.fp);
-    } else if (nslab > 64)
-        bn_finalize_kernel<64><<<cdiv(d.fp, 4), 256, 0, s>>>(sc.stats, nslab, d.fp, M, p->training, p->bn_eps,
-                                                               p->bn_momentum, sc.colp, pp, d.vc, w->bn, b->meta, tiles_per_wg, b->B, nullptr);
-    else
-        bn_finalize_kernel<16><<<cdiv(d.fp, 16), 256, 0, s>>>(sc.stats, nslab, d.fp, M, p->training, p->bn_eps,
-                                                                p->bn_momentum, sc.colp, pp, d.vc, w->bn, b->meta, tiles_per_wg, b->B, nullptr);
-    EAGCN_LAUNCH_CHECK();
+        EAGCN_BY_SLABS(nslab, bn_finalize_kernel, sync ? sc.gsum : sc.stats, nslab, d.fp, M, p->training, p->bn_eps, p->bn_momentum, sc.pk.colp,
+                       pp, d.vc, w->bn, b->meta, sync ? 0 : tiles_per_wg, b->B, sync ? sc.gsum + 2 * d.fp : nullptr);
+        EAGCN_LAUNCH_CHECK();
     }
     if (skip_apply) return EAGCN_OK;
-    return apply_launch(b, p, w, d, sc.colp, s, planes_only);
+    return apply_launch(b, p, w, d, sc.pk.colp, s, planes_only);
 }
 
+// both directions of layer p would take their input x from its bf16 plane images alone: the route of a call that brings them
 bool eagcn::layer_reads_planes_only(const eagcn_batch* b, const eagcn_layer_params* p, bool aux_stream) {
-    static const bool on = [] { const char* v = getenv("EAGCN_PLANES_ONLY"); return !(v && v[0] == '0'); }();
-    if (!on || aux_stream || !b || !p || b->T <= 0) return false;
-    const LayerDims d = layer_dims(b, p);
-    if (!d.np) return false;
-    // the three products exactly as layer_forward_impl / layer_backward_impl describe them (bx3_ok looks at alignment, strides
-    // and extents: the operands below stand for the 256-byte aligned pieces those functions carve)
-    const uint16_t* pl = reinterpret_cast<const uint16_t*>(static_cast<uintptr_t>(4096));
-    float* fo = reinterpret_cast<float*>(static_cast<uintptr_t>(4096));
-    const size_t xstride = bx_plane_elems(b->T, d.ld_in), pstride = bx_plane_elems(b->T, d.fp);
-    BxProb bp, bx, bw;
-    memset(&bp, 0, sizeof(bp)); memset(&bx, 0, sizeof(bx)); memset(&bw, 0, sizeof(bw));
-    bp.A = BxPlanes{pl, xstride, d.ld_in, b->T}; bp.B = BxPlanes{pl, d.wtpslab, d.ld_in, d.fp}; bp.C = fo; bp.ldc = d.fp;
-    bp.M = b->T; bp.N = d.fp; bp.K = d.ld_in; bp.M_dev = b->meta + EAGCN_META_T; bp.tn = 0; bp.splits = 1;
-    bx.A = BxPlanes{pl, pstride, d.fp, b->T}; bx.B = BxPlanes{pl, d.wpslab, d.fp, d.ld_in}; bx.C = fo; bx.ldc = d.ld_in;
-    bx.M = b->T; bx.N = d.ld_in; bx.K = d.fp; bx.M_dev = b->meta + EAGCN_META_T; bx.tn = 0; bx.splits = 1;
-    bw.A = BxPlanes{pl, xstride, d.ld_in, b->T}; bw.B = BxPlanes{pl, pstride, d.fp, b->T};
-    bw.C = fo; bw.ldc = d.fp; bw.M = d.ld_in; bw.N = d.fp; bw.K = b->T; bw.K_dev = b->meta + EAGCN_META_T; bw.tn = 1;
-    bw.splits = d.bx_splits; bw.slab = d.wslab;
-    return bx3_ok(bp) && bx3_ok(bw) && bx3_ok(bx);
+    if (!sw_planes_only() || aux_stream || !b || !p || b->T <= 0) return false;
+    // (bx3_ok looks at alignment, strides and extents: the addresses stand for the 256-byte aligned pieces the executors carve)
+    void* const some = reinterpret_cast<void*>(static_cast<uintptr_t>(4096));
+    eagcn_layer_bufs w;
+    memset(&w, 0, sizeof(w));
+    w.x_planes = static_cast<const uint16_t*>(some); w.P = static_cast<float*>(some); w.scratch = some;
+    const LayerRoute r = plan_layer(b, p, &w, layer_dims(b, p), PlanAsk{true, false, false, false});
+    return r.fwd_prod == FWD_PLANES && r.bwd_prod == BWD_PLANES_PAIR;
 }
 
 int eagcn::layer_apply_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, void* stream) {
@@ -1158,45 +1313,6 @@ int eagcn::layer_apply_impl(const eagcn_batch* b, const eagcn_layer_params* p, c
     return apply_launch(b, p, w, d, pk.colp, (hipStream_t)stream);
 }
 
-static int apply_launch_(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const LayerDims& d,
-                         const float* colp, hipStream_t s, bool planes_only) {
-    ProfScope psbn(PROF_BN, s);
-    ApplyArgs aa;
-    aa.bt = *b; aa.vc = d.vc; aa.structure = p->structure; aa.fp = d.fp; aa.Y = w->Y; aa.ldy = d.fp;
-    aa.bn = w->bn; aa.colp = colp; aa.out = w->xout; aa.ldo = d.ldo; aa.pad_row = w->pad_row;
-    aa.do_drop = (p->training && p->dropout > 0.0f) ? 1 : 0;
-    aa.thr = (uint32_t)std::min(4294967295.0, (double)p->dropout * 4294967296.0);
-    aa.inv_keep = 1.0f / (1.0f - p->dropout);
-    aa.seed = p->seed;
-    aa.seed_dev = p->seed_dev;
-    aa.planes = BxOut{gemm_planes() ? w->xout_planes : nullptr, bx_plane_elems(b->T, d.ldo), gemm_planes(), b->T};
-    if (planes_only && aa.planes.p) aa.out = nullptr;        // (the only reader is the layer above, through the planes)
-    static const int map_env = [] { const char* v = getenv("EAGCN_BN_APPLY_MAP"); return v ? atoi(v) : -1; }();
-    aa.tile_map = map_env >= 0 ? map_env : (aa.planes.p ? 1 : 0);
-    const size_t nthr = aa.tile_map ? (size_t)cdiv(std::max(b->T, 1), 8) * cdiv(d.ldo, 32) * 64 : (size_t)std::max(b->T, 1) * d.ldo / 4;
-    bn_apply_kernel<<<ew_grid(nthr), 256, 0, s>>>(aa);
-    EAGCN_LAUNCH_CHECK();
-    return EAGCN_OK;
-}
-
-// Second pass of the BatchNorm backward: re-form dH in the reduction kernel's body (APPLY) or read the dH the first pass stored
-// (elementwise bn_bwd_apply_kernel).  Weighted_sum: the upstream gradient is K times narrower than dH, re-forming it saves a
-// write and a read of T x Fp floats (HIV widths: 9.74 -> 9.53 ms per step).  Concate: the upstream gradient is as wide as dH
-// and the plain elementwise pass is the lighter kernel (B = 256: 0.456 vs 0.459 ms; B = 1024: equal).
-// EAGCN_BWD_STORE_DH=1 / 0 forces one or the other.
-// the elementwise second pass of the BatchNorm backward disappears into lagg.hip's staging whenever that kernel consumes dY' (it is
-// the ONLY consumer then: transposed aggregation and edge gradients in one launch); EAGCN_LAGG_FUSE_BN=0 keeps the pass
-static bool lagg_fuses_bn() {
-    static const bool on = [] { const char* v = getenv("EAGCN_LAGG_FUSE_BN"); return !(v && v[0] == '0'); }();
-    return on;
-}
-// Weighted_sum layers (round 6): lagg.hip re-forms dH from the K-times-narrower upstream gradient in its staging, so the second pass
-// (a read of Y' and a write of T x K F floats) and the read of dY' behind it disappear; EAGCN_LAGG_WFUSE=0 keeps the pass
-// (lagg_wfuse(): lagg.hip, where the policy lives)
-static bool bn_bwd_two_pass(bool weighted) {
-    static const int force = [] { const char* v = getenv("EAGCN_BWD_STORE_DH"); return v ? (v[0] == '1' ? 1 : 0) : -1; }();
-    return force < 0 ? weighted : force == 0;
-}
 // the two passes of bn_bwd_reduce_kernel (apply = false: sums, apply = true: dY') in their compile-time variants
 static void launch_bn_bwd_pass(bool apply, bool wt, bool dg, bool dr, dim3 grid, const BwdArgs& ba, hipStream_t s) {
 #define EAGCN_BWD(W, G, D) do { if (apply) bn_bwd_reduce_kernel<W, G, D, true><<<grid, 256, 0, s>>>(ba); \
@@ -1212,345 +1328,274 @@ extern "C" int eagcn_layer_backward(const eagcn_batch* b, const eagcn_layer_para
                                     const float* dxout, const float* dpad_row, float* dx,
                                     const eagcn_layer_grads* g, void* stream) {
     EAGCN_CHECK_GEMM3("eagcn_layer_backward");
-    if (w && w->scratch && w->scratch_bytes >= gemm3_workspace_bytes()) {
-        int rc = gemm3_clear_flags(w->scratch, w->scratch_bytes, (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    return layer_backward_impl(b, p, w, dxout, nullptr, dpad_row, dx, g, stream);
+    const int rc = clear_handoff_flags(w, stream);
+    return rc ? rc : layer_backward_impl(b, p, w, dxout, dpad_row, dx, g, stream);
 }
 
-int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w,
-                               const float* dxout, const ReadoutGrad* rg, const float* dpad_row, float* dx,
-                               const eagcn_layer_grads* g, void* stream, bool dpad_views, const ZeroJob* zero_after,
-                               const EdgeDrain* drain_in, EdgeDrain* drain_out, bool input_only) {
-    if (drain_out) drain_out->eacc = nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    int rc = check_layer(b, p, "eagcn_layer_backward");
-    if (rc) return rc;
-    EAGCN_CHECK_ARG(w && (g || input_only) && w->bn && w->scratch, "eagcn_layer_backward: null buffer");
-    EAGCN_CHECK_ARG(!input_only || (dx && !drain_in), "eagcn_layer_backward: the input-only form needs dx and takes no edge reduction");
-    EAGCN_CHECK_ARG(b->T == 0 || ((dxout || rg) && (input_only || w->x || w->x_planes) && w->P && w->Y && w->rscale),
-                    "eagcn_layer_backward: null activation buffer");
-    if (!input_only)
-        for (int k = 0; k < p->K; ++k)
-            EAGCN_CHECK_ARG(g->dW[k] && g->dbias[k] && g->dgamma[k] && g->dbeta[k] && g->datt_w[k] && g->dself_r[k],
-                            "eagcn_layer_backward: view %d has a null gradient buffer", k);
-    const LayerDims d = layer_dims(b, p);
-    BwdScratch sc;
-    const size_t need = carve_bwd(w->scratch, b, d, &sc);
-    if (need > w->scratch_bytes) {
-        set_error("eagcn_layer_backward: scratch too small (%zu < %zu)", w->scratch_bytes, need);
-        return EAGCN_ERR_SCRATCH;
-    }
-    const ParamPtrs pp = param_ptrs(b, p);
-    GradPtrs gp;
-    memset(&gp, 0, sizeof(gp));
-    if (input_only) {
-        // (a training-mode BatchNorm finalize still writes d gamma / d beta / d bias / d ave.weight on its way: into the weight-gradient
-        //  slab area, which this form does not use; nothing reads them)
-        EAGCN_CHECK_ARG(d.wslab >= (size_t)3 * d.fp + EAGCN_MAX_VIEWS, "eagcn_layer_backward: no room for the discarded BatchNorm gradients");
-        for (int k = 0; k < p->K; ++k) {
-            gp.dgamma[k] = sc.dWcat + d.vc.off[k];
-            gp.dbeta[k] = sc.dWcat + d.fp + d.vc.off[k];
-            gp.dbias[k] = sc.dWcat + 2 * d.fp + d.vc.off[k];
-        }
-        gp.dave_w = p->structure == EAGCN_STRUCT_WEIGHTED ? sc.dWcat + 3 * d.fp : nullptr;
-    } else {
-        for (int k = 0; k < p->K; ++k) {
-            gp.dW[k] = g->dW[k]; gp.dbias[k] = g->dbias[k]; gp.dgamma[k] = g->dgamma[k]; gp.dbeta[k] = g->dbeta[k];
-            gp.datt_w[k] = g->datt_w[k]; gp.dself_r[k] = g->dself_r[k];
-        }
-        gp.dave_w = p->structure == EAGCN_STRUCT_WEIGHTED ? g->dave_w : nullptr;
-    }
-    const ColMapD in = make_colmap(&p->in);
-    if (w->packed) {          // parameters were re-laid by the forward call and kept
-        Packed pk;
-        const size_t pneed = carve_packed(w->packed, d, &pk);
-        if (pneed > w->packed_bytes) {
-            set_error("eagcn_layer_backward: packed buffer too small (%zu < %zu)", w->packed_bytes, pneed);
-            return EAGCN_ERR_SCRATCH;
-        }
-        sc.Wcat = pk.Wcat; sc.WcatT = pk.WcatT; sc.colp = pk.colp; sc.sig = pk.sig; sc.rsig = pk.rsig;
-        sc.Wp = pk.Wp; sc.WTp = pk.WTp;
-    } else {
-        ProfScope ps(PROF_PACK, s);
-        pack_params_kernel<<<ew_grid(d.wslab), 256, 0, s>>>(pp, d.vc, in, d.ld_in, d.fp, sc.Wcat, sc.WcatT, sc.colp, sc.sig, sc.rsig,
-                                                            BxOut{d.np ? sc.Wp : nullptr, d.wpslab, d.np, d.ld_in},
-                                                            BxOut{d.np ? sc.WTp : nullptr, d.wtpslab, d.np, d.fp});
-    }
-    EAGCN_LAUNCH_CHECK();
-    double fsum = 0.0;
-    for (int k = 0; k < p->K; ++k) fsum += p->width[k];
-    const double gemm_work = 2.0 * (double)b->T * (double)d.fin * fsum;
-
-    BwdArgs ba;
-    ba.meta = b->meta; ba.Tcap = b->T; ba.row_mol = b->row_mol; ba.row_m = b->row_m;
-    ba.vc = d.vc; ba.structure = p->structure; ba.fp = d.fp;
-    ba.nvirt = (dpad_row && p->structure == EAGCN_STRUCT_WEIGHTED) ? 1 : 0;
-    ba.dxout = dxout; ba.ldo = d.ldo; ba.dpad = dpad_row; ba.dpad_views = dpad_views ? 1 : 0;
-    if (rg) ba.rg = *rg; else memset(&ba.rg, 0, sizeof(ba.rg)); ba.Y = w->Y; ba.ldy = d.fp; ba.bn = w->bn;
-    ba.colp = sc.colp; ba.dH = sc.dY; ba.slab = sc.slab; ba.slab_da = sc.slab_da;
-    ba.do_drop = (p->training && p->dropout > 0.0f) ? 1 : 0;
-    ba.thr = (uint32_t)std::min(4294967295.0, (double)p->dropout * 4294967296.0);
-    ba.inv_keep = 1.0f / (1.0f - p->dropout);
-    ba.seed = p->seed;
-    ba.seed_dev = p->seed_dev;
-    ba.zero = zero_after ? zero_after->d : nullptr;
-    ba.nzero = zero_after ? zero_after->nd : 0;
-    if (drain_in && drain_in->eacc) ba.drain = *drain_in; else memset(&ba.drain, 0, sizeof(ba.drain));
-    const int rows = b->T + ba.nvirt;
-    const int gxb = std::max(1, std::min(rows, d.gxb));
-    bool fused_bn_apply = false, fused_w_apply = false, w_rows = false, fused_c_apply = false;
-    // the LDS-staged aggregation (lagg.hip) runs this layer's transposed aggregation + edge gradients: decided ONCE, here, because the
-    // BatchNorm backward below leaves its second pass to that kernel (the edge gradients must then leave through the shared accumulators)
-    bool lagg_bwd = false;
-    {
-        static const bool edge_atomic0 = [] { const char* v = getenv("EAGCN_EDGE_SLABS"); return !(v && v[0] == '1'); }();
-        bool general0 = false;
-        for (int k = 0; k < p->K; ++k) general0 = general0 || pp.rel_vec[k] != nullptr;
-        const bool wt0 = p->structure == EAGCN_STRUCT_WEIGHTED;
-        const bool absorbs = lagg_fuses_bn() && (!bn_bwd_two_pass(wt0) || (wt0 && lagg_wfuse()));
-        lagg_bwd = b->T > 0 && edge_atomic0 && !general0 && lagg_use(b, 1, absorbs);
-        // input-only: no edge gradients to route, and the staging absorbs the BatchNorm backward whatever the structure
-        if (input_only) lagg_bwd = b->T > 0 && lagg_use(b, 1, true);
-    }
-    const double M = (double)b->B * (double)b->N;
-    const bool eval_in = input_only && !p->training;
-    if (eval_in) {
-        // eval-mode BatchNorm backward of the input-only form: dY' = sc dH (the running statistics are constants: c1 = c2 = 0), no
-        // reduction and no finalize.  With the LDS-staged aggregation dH and dY' are formed in its staging from the upstream gradient
-        // (a per-molecule read-out gradient is written as rows first); otherwise the reduction kernel's APPLY pass forms dY' from zero means
-        const bool wt = p->structure == EAGCN_STRUCT_WEIGHTED, dg = ba.rg.dg != nullptr;
-        if (b->T > 0 && lagg_bwd) {
-            if (dg) {
-                rc = launch_readout_bwd_rows(b, ba.rg, d.ldo, sc.dY, s);
-                if (rc) return rc;
-                w_rows = true;
-            }
-            if (wt) fused_w_apply = true; else fused_c_apply = true;
-        } else if (b->T > 0) {
-            rc = zero_fill(sc.cc, (size_t)2 * d.fp * sizeof(float), s);
-            if (rc) return rc;
-            ba.cc = sc.cc;
-            launch_bn_bwd_pass(true, wt, dg, false, dim3(std::max(1, std::min(b->T, d.gxb)), cdiv(d.fp, 1024)), ba, s);
-            EAGCN_LAUNCH_CHECK();
-        }
-        // (the head's backward sums are left zero for a later backward call: the finalize that clears them on the way did not run)
-        if (zero_after && zero_after->nd) { rc = zero_fill(zero_after->d, (size_t)zero_after->nd * sizeof(double), s); if (rc) return rc; }
-    } else {
-        ProfScope ps(PROF_BN, s);
-        const int ny = cdiv(d.fp, 1024);
-        {
-            const bool wt = p->structure == EAGCN_STRUCT_WEIGHTED, dr = ba.do_drop != 0;
-            bool dg = ba.rg.dg != nullptr;
-            const dim3 grid(gxb, ny);
-            ba.cc = sc.cc;
-            ba.store_dh = bn_bwd_two_pass(wt) ? 0 : 1;
-            // Weighted_sum top layer whose dH is re-formed in lagg.hip's staging: that kernel wants the per-molecule read-out gradient as
-            // ROWS ([T][ldo], K times narrower than dH) -- written first, so that this pass reads them with 16-byte loads as well
-            // instead of gathering dg[molecule] element by element (fingerprint widths are not multiples of four: HIV 250)
-            static const bool rows_first = [] { const char* v = getenv("EAGCN_W_ROWS_FIRST"); return !(v && v[0] == '0'); }();
-            if (wt && dg && b->T > 0 && bn_bwd_two_pass(wt) && lagg_bwd && lagg_fuses_bn() && lagg_wfuse() && rows_first) {
-                rc = launch_readout_bwd_rows(b, ba.rg, d.ldo, sc.dY, s);
-                if (rc) return rc;
-                w_rows = true;
-                ba.dxout = sc.dY;
-                dg = false;
-            }
-            launch_bn_bwd_pass(false, wt, dg, dr, grid, ba, s);
-        }
-        EAGCN_LAUNCH_CHECK();
-        const double* gsum = nullptr;
-        if (w->stats_hook && p->training) {
-            // sync-BatchNorm: sum dH, sum dH xhat and the row count of this rank -> summed across the ranks by the caller's hook
-            if (gxb > 64) bn_stats_sum_kernel<64><<<cdiv(d.fp, 4), 256, 0, s>>>(sc.slab, gxb, d.fp, M, sc.gsum, b->meta, 2, 0, ba.nvirt, b->B);
-            else bn_stats_sum_kernel<16><<<cdiv(d.fp, 16), 256, 0, s>>>(sc.slab, gxb, d.fp, M, sc.gsum, b->meta, 2, 0, ba.nvirt, b->B);
-            EAGCN_LAUNCH_CHECK();
-            if (w->stats_hook(sc.gsum, 2 * d.fp + 1, stream, w->stats_user)) {
-                set_error("eagcn_layer_backward: the sync-BatchNorm all-reduce hook failed");
-                return EAGCN_ERR_HIP;
-            }
-            gsum = sc.gsum;
-        }
-        if (gxb > 64)
-            bn_bwd_finalize_kernel<64><<<cdiv(d.fp, 4), 256, 0, s>>>(sc.slab, sc.slab_da, gxb, d.fp, M, p->training, w->bn,
-                                                                       d.vc, gp, sc.cc, b->meta, ba.nvirt, b->B, ny, gxb, gsum, ba.zero, ba.nzero);
-        else
-            bn_bwd_finalize_kernel<16><<<cdiv(d.fp, 16), 256, 0, s>>>(sc.slab, sc.slab_da, gxb, d.fp, M, p->training, w->bn,
-                                                                        d.vc, gp, sc.cc, b->meta, ba.nvirt, b->B, ny, gxb, gsum, ba.zero, ba.nzero);
-        EAGCN_LAUNCH_CHECK();
-        if (b->T > 0) {
-            // second pass of the same kernel body: dH formed again, dY' written (sc.dY)
-            const bool wt = p->structure == EAGCN_STRUCT_WEIGHTED, dg = ba.rg.dg != nullptr, dr = ba.do_drop != 0;
-            if (bn_bwd_two_pass(wt) && wt && lagg_bwd && lagg_fuses_bn() && lagg_wfuse()) {
-                fused_w_apply = true;                                           // the LDS-staged aggregation forms dH AND dY' in its staging
-                if (dg && !w_rows) {                                                       // (per-molecule upstream gradient: its rows, once, K times narrower than dH)
-                    rc = launch_readout_bwd_rows(b, ba.rg, d.ldo, sc.dY, s);
-                    if (rc) return rc;
-                }
-            } else if (bn_bwd_two_pass(wt)) launch_bn_bwd_pass(true, wt, dg, dr, dim3(std::max(1, std::min(b->T, d.gxb)), ny), ba, s);
-            else if (lagg_bwd && lagg_fuses_bn()) fused_bn_apply = true;      // the LDS-staged aggregation forms dY' from the stored dH while it stages its rows
-            else bn_bwd_apply_kernel<<<ew_grid((size_t)b->T * d.fp / 4), 256, 0, s>>>(*b, d.fp, w->Y, d.fp, w->bn, sc.cc, sc.dY);
-            EAGCN_LAUNCH_CHECK();
-        }
-    }
-    int nsplit = 0, nedge = 0, xk_G = 0;
+namespace {
+// one backward call: its arguments, carving and route, and what the products leave for unpack_grads
+struct LayerBwd {
+    const eagcn_batch* b; const eagcn_layer_params* p; const eagcn_layer_bufs* w;
+    const float* dxout; const float* dpad_row; float* dx; LayerBwdOpts o;
+    LayerDims d; LayerScratch sc; LayerRoute r; ParamPtrs pp; GradPtrs gp; ColMapD in;
+    hipStream_t s, side;         // side: work that is off the dX critical path (edge gradients, dW product, gradient unpacking);
+    bool forked;                 // with no auxiliary stream everything stays in order on s
+    bool wt, dg; DropArgs drop; double gemm_work;
+    int nsplit = 0, xk_G = 0;
     bool bx_slabs = false;       // dWcat holds the k-chunk slabs of the plane GEMM (all of them written)
     int bx_per = 0;              // > 0: that product shared its launch with dX (workgroups per XCD: bx3.h bx3_used_splits)
     int bx_wide = 0;             // ... and which of the two plane-GEMM kernels wrote the slabs (the chunk policy counts ITS tiles)
-    // side = stream for work that is off the dX critical path (edge gradients, dW product, gradient
-    // unpacking); with no auxiliary stream everything stays in order on s
-    hipStream_t side = w->aux_stream ? (hipStream_t)w->aux_stream : s;
-    const bool forked = side != s;
-    if (b->T > 0) {
-        AggArgs a;
-        a.bt = *b; a.vc = d.vc; a.src = sc.dY; a.lds = d.fp; a.dst = sc.dP; a.ldd = d.fp;
-        a.sig = sc.sig; a.rsig = sc.rsig; a.rscale = w->rscale; a.stats = nullptr; a.nchunk = 1;
-        // plane GEMMs (gemm_bx3.hip): dX = dP.Wcat^T (NT) and dW = X^T.dP (TN, k-chunk slabs summed by unpack_grads) in one
-        // persistent launch; dP leaves the transposed aggregation as bf16 planes and is never written as fp32
-        const size_t xstride = bx_plane_elems(b->T, d.ld_in), pstride = bx_plane_elems(b->T, d.fp);
-        BxProb bx, bw;
-        memset(&bx, 0, sizeof(bx));
-        memset(&bw, 0, sizeof(bw));
-        bool use_bx = false;
-        if (d.np && !w->aux_stream) {
-            bx.A = BxPlanes{sc.dPp, pstride, d.fp, b->T}; bx.B = BxPlanes{sc.Wp, d.wpslab, d.fp, d.ld_in}; bx.C = dx; bx.ldc = d.ld_in;
-            bx.M = b->T; bx.N = d.ld_in; bx.K = d.fp; bx.M_dev = b->meta + EAGCN_META_T; bx.tn = 0; bx.splits = 1;
-            bw.A = BxPlanes{w->x_planes ? w->x_planes : sc.xp, xstride, d.ld_in, b->T}; bw.B = BxPlanes{sc.dPp, pstride, d.fp, b->T};
-            bw.C = sc.dWcat; bw.ldc = d.fp; bw.M = d.ld_in; bw.N = d.fp; bw.K = b->T; bw.K_dev = b->meta + EAGCN_META_T; bw.tn = 1;
-            bw.splits = d.bx_splits; bw.slab = d.wslab;
-            use_bx = bx3_ok(bw) && (!dx || bx3_ok(bx));
+};
+}  // namespace
+
+// where the parameter gradients go; input-only: a training-mode BatchNorm finalize still writes d gamma / d beta / d bias /
+// d ave.weight on its way -- into the weight-gradient slab area, which that form does not use; nothing reads them
+static GradPtrs grad_ptrs(const eagcn_layer_params* p, const eagcn_layer_grads* g, const LayerDims& d, float* discard) {
+    GradPtrs gp;
+    memset(&gp, 0, sizeof(gp));
+    for (int k = 0; k < p->K; ++k) {
+        if (discard) {
+            gp.dgamma[k] = discard + d.vc.off[k];
+            gp.dbeta[k] = discard + d.fp + d.vc.off[k];
+            gp.dbias[k] = discard + 2 * d.fp + d.vc.off[k];
+        } else {
+            gp.dW[k] = g->dW[k]; gp.dbias[k] = g->dbias[k]; gp.dgamma[k] = g->dgamma[k]; gp.dbeta[k] = g->dbeta[k];
+            gp.datt_w[k] = g->datt_w[k]; gp.dself_r[k] = g->dself_r[k];
         }
-        if (use_bx) {
-            a.planes = BxOut{sc.dPp, pstride, d.np, b->T};
-            if (!w->x_planes && !input_only) {
-                rc = launch_bx3_split(w->x, b->T, b->meta + EAGCN_META_T, d.ld_in, sc.xp, xstride, b->T, d.np, s);
-                if (rc) return rc;
-            }
-        } else if (!w->x && !input_only) {
+    }
+    gp.dave_w = p->structure != EAGCN_STRUCT_WEIGHTED ? nullptr : discard ? discard + 3 * d.fp : g->dave_w;
+    return gp;
+}
+
+// BatchNorm backward up to where the route leaves dY' (or what lagg.hip's staging forms it from) in sc.dY
+static int bwd_batchnorm(LayerBwd& c) {
+    const eagcn_batch* b = c.b; const eagcn_layer_params* p = c.p; const eagcn_layer_bufs* w = c.w;
+    const LayerDims& d = c.d; const LayerScratch& sc = c.sc; const LayerRoute& r = c.r; hipStream_t s = c.s;
+    BwdArgs ba;
+    ba.meta = b->meta; ba.Tcap = b->T; ba.row_mol = b->row_mol; ba.row_m = b->row_m;
+    ba.vc = d.vc; ba.structure = p->structure; ba.fp = d.fp;
+    ba.nvirt = (c.dpad_row && c.wt) ? 1 : 0;
+    ba.dxout = c.dxout; ba.ldo = d.ldo; ba.dpad = c.dpad_row; ba.dpad_views = c.o.dpad_views ? 1 : 0;
+    if (c.o.rg) ba.rg = *c.o.rg; else memset(&ba.rg, 0, sizeof(ba.rg)); ba.Y = w->Y; ba.ldy = d.fp; ba.bn = w->bn;
+    ba.colp = sc.pk.colp; ba.dH = sc.dY; ba.slab = sc.slab; ba.slab_da = sc.slab_da;
+    ba.do_drop = c.drop.on; ba.thr = c.drop.thr; ba.inv_keep = c.drop.inv_keep; ba.seed = c.drop.seed; ba.seed_dev = c.drop.seed_dev;
+    const ZeroJob* za = c.o.zero_after;
+    ba.zero = za ? za->d : nullptr;
+    ba.nzero = za ? za->nd : 0;
+    if (c.o.drain_in && c.o.drain_in->eacc) ba.drain = *c.o.drain_in; else memset(&ba.drain, 0, sizeof(ba.drain));
+    ba.cc = sc.cc; ba.store_dh = r.store_dh ? 1 : 0;
+    const int ny = cdiv(d.fp, 1024);
+    const dim3 grid2(std::max(1, std::min(b->T, d.gxb)), ny);          // second pass: the stored rows alone
+    const bool dr = ba.do_drop != 0;
+    int rc;
+    if (c.o.input_only && !p->training) {
+        if (r.rows_first) { rc = launch_readout_bwd_rows(b, ba.rg, d.ldo, sc.dY, s); if (rc) return rc; }
+        if (r.bn2 == BN2_REDUCE_APPLY) {
+            rc = zero_fill(sc.cc, (size_t)2 * d.fp * sizeof(float), s);
+            if (rc) return rc;
+            launch_bn_bwd_pass(true, c.wt, c.dg, false, grid2, ba, s);
+            EAGCN_LAUNCH_CHECK();
+        }
+        // (the head's backward sums are left zero for a later backward call: the finalize that clears them on the way did not run)
+        return (za && za->nd) ? zero_fill(za->d, (size_t)za->nd * sizeof(double), s) : EAGCN_OK;
+    }
+    ProfScope ps(PROF_BN, s);
+    const double M = (double)b->B * (double)b->N;
+    const int gxb = std::max(1, std::min(b->T + ba.nvirt, d.gxb));
+    bool dg = c.dg;
+    if (r.rows_first) {
+        rc = launch_readout_bwd_rows(b, ba.rg, d.ldo, sc.dY, s);
+        if (rc) return rc;
+        ba.dxout = sc.dY;
+        dg = false;
+    }
+    launch_bn_bwd_pass(false, c.wt, dg, dr, dim3(gxb, ny), ba, s);
+    EAGCN_LAUNCH_CHECK();
+    const double* gsum = nullptr;
+    if (w->stats_hook && p->training) {
+        // sync-BatchNorm: sum dH, sum dH xhat and the row count of this rank -> summed across the ranks by the caller's hook
+        EAGCN_BY_SLABS(gxb, bn_stats_sum_kernel, sc.slab, gxb, d.fp, M, sc.gsum, b->meta, 2, 0, ba.nvirt, b->B);
+        EAGCN_LAUNCH_CHECK();
+        if (w->stats_hook(sc.gsum, 2 * d.fp + 1, (void*)s, w->stats_user)) {
+            set_error("eagcn_layer_backward: the sync-BatchNorm all-reduce hook failed");
+            return EAGCN_ERR_HIP;
+        }
+        gsum = sc.gsum;
+    }
+    EAGCN_BY_SLABS(gxb, bn_bwd_finalize_kernel, sc.slab, sc.slab_da, gxb, d.fp, M, p->training, w->bn, d.vc, c.gp, sc.cc, b->meta, ba.nvirt,
+                   b->B, ny, gxb, gsum, ba.zero, ba.nzero);
+    EAGCN_LAUNCH_CHECK();
+    if (r.rows_late) { rc = launch_readout_bwd_rows(b, ba.rg, d.ldo, sc.dY, s); if (rc) return rc; }
+    if (r.bn2 == BN2_REDUCE_APPLY) launch_bn_bwd_pass(true, c.wt, c.dg, dr, grid2, ba, s);       // dH formed again, dY' written
+    else if (r.bn2 == BN2_ELEMENTWISE)
+        bn_bwd_apply_kernel<<<ew_grid((size_t)b->T * d.fp / 4), 256, 0, s>>>(*b, d.fp, w->Y, d.fp, w->bn, sc.cc, sc.dY);
+    EAGCN_LAUNCH_CHECK();
+    return EAGCN_OK;
+}
+
+// transposed aggregation dP (fp32, or bf16 planes for the plane GEMMs) and, in the full form, the edge gradients
+static int bwd_aggregate(LayerBwd& c) {
+    const eagcn_batch* b = c.b; const eagcn_layer_bufs* w = c.w; const LayerDims& d = c.d; const LayerScratch& sc = c.sc;
+    const LayerRoute& r = c.r; hipStream_t s = c.s;
+    int rc;
+    AggArgs a;
+    a.bt = *b; a.vc = d.vc; a.src = sc.dY; a.lds = d.fp; a.dst = sc.dP; a.ldd = d.fp;
+    a.sig = sc.pk.sig; a.rsig = sc.pk.rsig; a.rscale = w->rscale; a.stats = nullptr; a.nchunk = 1;
+    if (r.bwd_planes()) a.planes = BxOut{sc.dPp, bx_plane_elems(b->T, d.fp), d.np, b->T};
+    if (r.bn2_staged()) {        // lagg.hip forms dY' while it stages its rows (eval mode: zero means, no table of them)
+        a.bn_tab = w->bn; a.bn_cc = (c.o.input_only && !c.p->training) ? nullptr : sc.cc; a.bn_fp = d.fp;
+    }
+    if (r.bn2 == BN2_STAGED_FROM_UPSTREAM || r.bn2 == BN2_STAGED_ROWMASK) {      // ... and dH before it, from the upstream gradient
+        a.src = c.dg ? sc.dY : c.dxout; a.lds = d.ldo;
+        a.w_aw = sc.pk.colp + (size_t)CP_AVEW * d.fp;
+        a.w_rowm = r.bn2 == BN2_STAGED_ROWMASK;
+        agg_set_drop(a, c.drop);
+    }
+    EdgeArgs e;
+    e.bt = *b; e.vc = d.vc; e.dY = sc.dY; e.Y = w->Y; e.P = w->P; e.ld = d.fp; e.sig = sc.pk.sig;
+    e.rsig = sc.pk.rsig; e.rscale = w->rscale; e.datt = r.edge_atomic ? sc.eacc : sc.datt; e.atomic = r.edge_atomic ? 1 : 0;
+    switch (r.edge) {
+    case EDGE_NONE:              // input-only (agg.hip: molecules of more than 256 atoms, code books)
+        return r.bwd_agg == AGG_LAGG ? launch_lagg_bwd(a, e, s, false) : launch_agg(a, true, s);
+    case EDGE_WITH_LAGG: return launch_lagg_bwd(a, e, s);       // both from the same LDS gathers
+    case EDGE_COLAUNCH: return launch_agg_edge(a, e, s);        // one grid for both
+    default:
+        if (c.forked) { rc = stream_after(c.side, s); if (rc) return rc; }      // dY' is ready
+        rc = launch_edge_grad(e, c.side);
+        return rc ? rc : launch_agg(a, true, s);
+    }
+}
+
+// dX = dP.Wcat^T and dW = X^T.dP
+static int bwd_products(LayerBwd& c, const LayerOperands& o) {
+    const eagcn_batch* b = c.b; const LayerDims& d = c.d; const LayerScratch& sc = c.sc; hipStream_t s = c.s;
+    const PlaneProducts bq = layer_plane_products(b, d, o);
+    const Fp32Products gq = layer_fp32_products(b, d, o, c.gemm_work);
+    DwScatter dsc;
+    for (int k = 0; k < EAGCN_MAX_VIEWS; ++k) dsc.dW[k] = c.gp.dW[k];
+    dsc.vc = d.vc;
+    dsc.in = c.in;
+    int rc;
+    c.nsplit = d.nsplit;
+    switch (c.r.bwd_prod) {
+    case BWD_PLANES_DX: return launch_bx3(bq.bx, nullptr, d.np, s, c.gemm_work, PROF_GEMM, bx3_pick_wide(bq.bx, nullptr, b->t_hint));
+    case BWD_TILED_DX: return launch_gemm(gq.gx, s);
+    case BWD_PLANES_PAIR:
+        c.bx_wide = bx3_pick_wide(bq.bx, &bq.bw, b->t_hint);
+        rc = launch_bx3(bq.bx, &bq.bw, d.np, s, 2.0 * c.gemm_work, PROF_GEMM_PAIR, c.bx_wide);
+        c.nsplit = d.bx_splits;                       // partial slabs of dWcat: summed and scattered by unpack_grads
+        c.bx_slabs = true;
+        c.bx_per = bx3_pair_policy() ? std::max(1, bx3_grid() >> 3) : 0;
+        return rc;
+    case BWD_PLANES_DW:
+        c.bx_wide = bx3_pick_wide(bq.bw, nullptr, b->t_hint);
+        rc = launch_bx3(bq.bw, nullptr, d.np, s, c.gemm_work, PROF_GEMM, c.bx_wide);
+        c.nsplit = d.bx_splits;
+        c.bx_slabs = true;
+        return rc;
+    case BWD_G3_XK:              // every XCD works on its own eighth of the packed rows for BOTH products
+        rc = launch_gemm3_pair(gq.gx, gq.gw, nullptr, sc.gws, gemm3_workspace_bytes(), s, d.wslab);
+        c.nsplit = 1;
+        c.xk_G = gemm3_grid();
+        return rc;
+    case BWD_G3_SCATTER:
+        rc = launch_gemm3_pair(gq.gx, gq.gw, &dsc, sc.gws, gemm3_workspace_bytes(), s);
+        c.nsplit = 0;                                 // no partial slabs: unpack_grads only reduces the edge partials
+        return rc;
+    case BWD_TILED_PAIR: return launch_gemm_pair(gq.gx, gq.gw, s);              // dX and dW share one grid
+    default:
+        rc = launch_gemm(gq.gw, c.side);
+        return (rc || !c.dx) ? rc : launch_gemm(gq.gx, s);
+    }
+}
+
+// dW slabs summed and scattered into the per-view gradients, edge partials reduced -- or that reduction handed down
+static int bwd_unpack(LayerBwd& c) {
+    const eagcn_batch* b = c.b; const eagcn_layer_params* p = c.p; const LayerDims& d = c.d; const LayerScratch& sc = c.sc;
+    if (b->T == 0) {
+        // a batch without a single bond has no packed row: no product ran, the weight gradients are exactly zero (the edge
+        // partials below are summed over zero workgroups; the BatchNorm gradients came from the row-less reduction)
+        for (int k = 0; k < p->K; ++k)
+            { int rcz = zero_fill(c.gp.dW[k], (size_t)d.fin * p->width[k] * sizeof(float), c.side); if (rcz) return rcz; }
+    }
+    if (c.r.defer_drain) {
+        EdgeDrain* out = c.o.drain_out;
+        out->eacc = sc.eacc; out->K = p->K; out->rsig = sc.pk.rsig;
+        for (int k = 0; k < EAGCN_MAX_VIEWS; ++k) {
+            out->datt_w[k] = c.gp.datt_w[k]; out->dself_r[k] = c.gp.dself_r[k]; out->channels[k] = c.pp.channels[k];
+        }
+        return EAGCN_OK;
+    }
+    const int wblocks = c.nsplit > 0 ? cdiv((int)d.wslab, 256) : 0;     // (one thread per element: four lanes per four elements, unpack_grads)
+    const bool shared = b->T > 0 && c.r.edge_atomic;                    // shared accumulators: zeroed again by the threads that read them
+    const int nedge = b->T > 0 ? (shared ? -EDGE_COPIES : edge_grid_x(b)) : 0;
+    ProfScope psu(PROF_PACK, c.side);
+    unpack_grads_kernel<<<wblocks + cdiv(p->K * EDGE_SLAB, 16), 256, 0, c.side>>>(c.gp, c.pp, d.vc, c.in, d.ld_in, d.fp, sc.dWcat,
+                                                                                  c.bx_slabs ? -c.nsplit : c.nsplit, d.wslab,
+                                                                                  shared ? sc.eacc : sc.datt, nedge, sc.pk.rsig,
+                                                                                  wblocks, b->meta, c.xk_G, shared ? 1 : 0, c.bx_per, c.bx_wide);
+    EAGCN_LAUNCH_CHECK();
+    return EAGCN_OK;
+}
+
+int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w,
+                               const float* dxout, const float* dpad_row, float* dx, const eagcn_layer_grads* g, void* stream,
+                               const LayerBwdOpts& o) {
+    if (o.drain_out) o.drain_out->eacc = nullptr;
+    int rc = check_layer(b, p, "eagcn_layer_backward");
+    if (rc) return rc;
+    EAGCN_CHECK_ARG(w && (g || o.input_only) && w->bn && w->scratch, "eagcn_layer_backward: null buffer");
+    EAGCN_CHECK_ARG(!o.input_only || (dx && !o.drain_in), "eagcn_layer_backward: the input-only form needs dx and takes no edge reduction");
+    EAGCN_CHECK_ARG(b->T == 0 || ((dxout || o.rg) && (o.input_only || w->x || w->x_planes) && w->P && w->Y && w->rscale),
+                    "eagcn_layer_backward: null activation buffer");
+    if (!o.input_only)
+        for (int k = 0; k < p->K; ++k)
+            EAGCN_CHECK_ARG(g->dW[k] && g->dbias[k] && g->dgamma[k] && g->dbeta[k] && g->datt_w[k] && g->dself_r[k],
+                            "eagcn_layer_backward: view %d has a null gradient buffer", k);
+    LayerBwd c;
+    c.b = b; c.p = p; c.w = w; c.dxout = dxout; c.dpad_row = dpad_row; c.dx = dx; c.o = o;
+    c.d = layer_dims(b, p);
+    const LayerDims& d = c.d;
+    rc = carve_checked(b, w, d, true, &c.sc, "eagcn_layer_backward");      // (packed: re-laid by the forward call and kept)
+    if (rc) return rc;
+    if (o.input_only)
+        EAGCN_CHECK_ARG(d.wslab >= (size_t)3 * d.fp + EAGCN_MAX_VIEWS, "eagcn_layer_backward: no room for the discarded BatchNorm gradients");
+    c.s = (hipStream_t)stream;
+    c.side = w->aux_stream ? (hipStream_t)w->aux_stream : c.s;
+    c.forked = c.side != c.s;
+    c.wt = p->structure == EAGCN_STRUCT_WEIGHTED;
+    c.dg = o.rg && o.rg->dg;
+    c.pp = param_ptrs(b, p);
+    c.gp = grad_ptrs(p, g, d, o.input_only ? c.sc.dWcat : nullptr);
+    c.in = make_colmap(&p->in);
+    c.drop = drop_args(p->dropout, p->training != 0, p->seed, p->seed_dev);
+    c.gemm_work = layer_gemm_work(b, p, d);
+    if (!w->packed) launch_pack_params(c.pp, d, c.in, c.sc.pk, c.s);
+    EAGCN_LAUNCH_CHECK();
+    c.r = plan_layer(b, p, w, d, PlanAsk{dx != nullptr, c.dg, o.input_only, o.drain_out != nullptr});
+
+    rc = bwd_batchnorm(c);
+    if (rc) return rc;
+    if (b->T > 0) {
+        if (c.r.bwd_prod == BWD_REFUSED) {
             set_error("eagcn_layer_backward: the input exists as plane images only and the plane products do not apply");
             return EAGCN_ERR_ARG;
         }
-        EdgeArgs e;
-        e.bt = *b; e.vc = d.vc; e.dY = sc.dY; e.Y = w->Y; e.P = w->P; e.ld = d.fp; e.sig = sc.sig;
-        e.rsig = sc.rsig; e.rscale = w->rscale; e.datt = sc.datt; e.atomic = 0;
-        static const bool edge_atomic = [] { const char* v = getenv("EAGCN_EDGE_SLABS"); return !(v && v[0] == '1'); }();
-        bool general_rel = false;                     // (code books: the reduction reads a view's whole histogram per channel)
-        for (int k = 0; k < p->K; ++k) general_rel = general_rel || pp.rel_vec[k] != nullptr;
-        if (edge_atomic && !general_rel) { e.datt = sc.eacc; e.atomic = 1; }
-        static const bool colaunch = [] { const char* v = getenv("EAGCN_NO_COLAUNCH"); return !(v && v[0] == '1'); }();
-        nedge = e.atomic ? -EDGE_COPIES : edge_grid_x(b);
-        if (input_only) {
-            // ---- d(layer input) alone: the transposed aggregation without edge gradients, then dX = dP . Wcat^T as ONE product
-            if (lagg_bwd) {
-                if (fused_bn_apply || fused_w_apply || fused_c_apply) { a.bn_tab = w->bn; a.bn_cc = eval_in ? nullptr : sc.cc; a.bn_fp = d.fp; }
-                if (fused_w_apply || fused_c_apply) {
-                    a.src = (ba.rg.dg || w_rows) ? sc.dY : dxout; a.lds = d.ldo;
-                    a.w_aw = sc.colp + (size_t)CP_AVEW * d.fp;
-                    a.w_rowm = fused_c_apply;
-                    a.w_drop = ba.do_drop; a.w_thr = ba.thr; a.w_inv_keep = ba.inv_keep; a.w_seed = ba.seed; a.w_seed_dev = ba.seed_dev;
-                }
-                rc = launch_lagg_bwd(a, e, s, false);
-            } else {
-                rc = launch_agg(a, true, s);                                     // (agg.hip: molecules of more than 256 atoms, code books)
-            }
-            if (rc) return rc;
-            if (use_bx) {
-                rc = launch_bx3(bx, nullptr, d.np, s, gemm_work, PROF_GEMM, bx3_pick_wide(bx, nullptr, b->t_hint));
-            } else {
-                GemmDesc gx{0, 1, b->T, d.ld_in, d.fp, sc.dP, d.fp, sc.Wcat, d.fp, dx, d.ld_in, 1, 0, gemm_work};
-                gx.M_dev = b->meta + EAGCN_META_T;
-                rc = launch_gemm(gx, s);
-            }
-            return rc;
-        }
-        if (lagg_bwd && e.atomic) {                                              // transposed aggregation + edge gradients from the same LDS gathers
-            if (fused_bn_apply || fused_w_apply) { a.bn_tab = w->bn; a.bn_cc = sc.cc; a.bn_fp = d.fp; }
-            if (fused_w_apply) {
-                a.src = (ba.rg.dg || w_rows) ? sc.dY : dxout; a.lds = d.ldo;
-                a.w_aw = sc.colp + (size_t)CP_AVEW * d.fp;
-                a.w_drop = ba.do_drop; a.w_thr = ba.thr; a.w_inv_keep = ba.inv_keep; a.w_seed = ba.seed; a.w_seed_dev = ba.seed_dev;
-            }
-            rc = launch_lagg_bwd(a, e, s);
-            if (rc) return rc;
-        } else if (!forked && colaunch) {
-            rc = launch_agg_edge(a, e, s);                                       // one grid for both
-            if (rc) return rc;
-        } else {
-            if (forked) { rc = stream_after(side, s); if (rc) return rc; }      // dY' is ready
-            rc = launch_edge_grad(e, side);
-            if (rc) return rc;
-            rc = launch_agg(a, true, s);
+        if (c.r.bwd_split_x) {
+            rc = launch_bx3_split(w->x, b->T, b->meta + EAGCN_META_T, d.ld_in, c.sc.xp, bx_plane_elems(b->T, d.ld_in), b->T, d.np, c.s);
             if (rc) return rc;
         }
-        if (forked) { rc = stream_after(side, s); if (rc) return rc; }          // dP is ready
-        nsplit = d.nsplit;
-        GemmDesc gw{1, 0, d.ld_in, d.fp, b->T, w->x, d.ld_in, sc.dP, d.fp, sc.dWcat, d.fp, nsplit, d.wslab, gemm_work};
-        gw.K_dev = b->meta + EAGCN_META_T;
-        GemmDesc gx{0, 1, b->T, d.ld_in, d.fp, sc.dP, d.fp, sc.Wcat, d.fp, dx, d.ld_in, 1, 0, gemm_work};
-        gx.M_dev = b->meta + EAGCN_META_T;
-        static const bool pair = [] { const char* v = getenv("EAGCN_NO_PAIR"); return !(v && v[0] == '1'); }();
-        static const bool use3 = [] { const char* v = getenv("EAGCN_NO_GEMM3"); return !(v && v[0] == '1'); }();
-        DwScatter dsc;
-        for (int k = 0; k < EAGCN_MAX_VIEWS; ++k) dsc.dW[k] = gp.dW[k];
-        dsc.vc = d.vc;
-        dsc.in = in;
-        if (use_bx) {
-            bx_wide = dx ? bx3_pick_wide(bx, &bw, b->t_hint) : bx3_pick_wide(bw, nullptr, b->t_hint);
-            rc = dx ? launch_bx3(bx, &bw, d.np, s, 2.0 * gemm_work, PROF_GEMM_PAIR, bx_wide) : launch_bx3(bw, nullptr, d.np, s, gemm_work, PROF_GEMM, bx_wide);
-            if (rc) return rc;
-            nsplit = d.bx_splits;                         // partial slabs of dWcat: summed and scattered by unpack_grads below
-            bx_slabs = true;
-            bx_per = (dx && bx3_pair_policy()) ? std::max(1, bx3_grid() >> 3) : 0;
-        } else if (use3 && !forked && dx && gemm3_layer(d.ld_in) && gemm3_ok(gw) && gemm3_ok(gx) && gemm3_xk_enabled()) {
-            // wave-autonomous balanced kernel, XCD-local schedule: dX and dW in one launch, every XCD works on its own eighth of
-            // the packed rows for BOTH products; dW leaves as one partial slab per XCD, summed by unpack_grads below
-            rc = launch_gemm3_pair(gx, gw, nullptr, sc.gws, gemm3_workspace_bytes(), s, d.wslab);
-            if (rc) return rc;
-            nsplit = 1;
-            xk_G = gemm3_grid();
-        } else if (use3 && !forked && dx && gemm3_layer(d.ld_in) && gemm3_ok(gw) && gemm3_ok(gx)) {
-            // ... tile-contiguous schedule: dW written straight into the per-view gradients
-            rc = launch_gemm3_pair(gx, gw, &dsc, sc.gws, gemm3_workspace_bytes(), s);
-            if (rc) return rc;
-            nsplit = 0;                                   // no partial slabs: unpack_grads only reduces the edge partials
-        } else if (dx && !forked && colaunch && pair) {
-            rc = launch_gemm_pair(gx, gw, s);                                    // dX and dW share one grid
-            if (rc) return rc;
-        } else {
-            rc = launch_gemm(gw, side);
-            if (rc) return rc;
-            if (dx) { rc = launch_gemm(gx, s); if (rc) return rc; }
-        }
+        rc = bwd_aggregate(c);
+        if (rc) return rc;
+        if (c.forked && !o.input_only) { rc = stream_after(c.side, c.s); if (rc) return rc; }          // dP is ready
+        rc = bwd_products(c, layer_operands(w, c.sc, dx));
+        if (rc) return rc;
     }
-    if (b->T == 0 && input_only) return EAGCN_OK;          // (no packed row: d(layer input) has no entry)
-    if (b->T == 0) {
-        // a batch without a single bond has no packed row: no product ran, the weight gradients are exactly zero (the edge
-        // partials below are summed over zero workgroups; the BatchNorm gradients came from the row-less reduction above)
-        for (int k = 0; k < p->K; ++k)
-            { int rcz = zero_fill(gp.dW[k], (size_t)d.fin * p->width[k] * sizeof(float), side); if (rcz) return rcz; }
-    }
-    {
-        const int wblocks = nsplit > 0 ? cdiv((int)d.wslab, 256) : 0;     // (one thread per element: four lanes per four elements, unpack_grads)
-        double* edge_src = nedge == -EDGE_COPIES ? sc.eacc : sc.datt;
-        const int edge_drain = edge_src == sc.eacc ? 1 : 0;       // shared accumulators: zeroed again by the threads that read them
-        static const bool defer_env = [] { const char* v = getenv("EAGCN_NO_EDGE_DEFER"); return !(v && v[0] == '1'); }();
-        if (defer_env && drain_out && edge_drain && wblocks == 0 && !forked && b->T > 0) {
-            // nothing but the edge reduction is left for this layer: the next layer's first backward kernel does it (one launch less)
-            drain_out->eacc = sc.eacc; drain_out->K = p->K; drain_out->rsig = sc.rsig;
-            for (int k = 0; k < EAGCN_MAX_VIEWS; ++k) {
-                drain_out->datt_w[k] = gp.datt_w[k]; drain_out->dself_r[k] = gp.dself_r[k]; drain_out->channels[k] = pp.channels[k];
-            }
-            return EAGCN_OK;
-        }
-        ProfScope psu(PROF_PACK, side);
-        unpack_grads_kernel<<<wblocks + cdiv(p->K * EDGE_SLAB, 16), 256, 0, side>>>(gp, pp, d.vc, in, d.ld_in, d.fp, sc.dWcat,
-                                                                                    bx_slabs ? -nsplit : nsplit, d.wslab, edge_src, nedge, sc.rsig,
-                                                                                    wblocks, b->meta, xk_G, edge_drain, bx_per, bx_wide);
-        EAGCN_LAUNCH_CHECK();
-    }
+    if (o.input_only) return EAGCN_OK;                 // (no parameter gradient is formed)
+    rc = bwd_unpack(c);
+    if (rc) return rc;
     // join: the caller reuses the scratch block (dY', dP, partial slabs) for the next layer
-    if (forked) { rc = stream_after(s, side); if (rc) return rc; }
+    if (c.forked && !c.r.defer_drain) { rc = stream_after(c.s, c.side); if (rc) return rc; }
     return EAGCN_OK;
 }
 

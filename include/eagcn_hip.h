@@ -221,7 +221,7 @@ int eagcn_agg_wants_bond_lists(int B, int N);
 int eagcn_agg_wants_bond_lists_for(int B, int N, int structure);
 
 /* ---- library ------------------------------------------------------------------------------- */
-int eagcn_abi_version(void);           /* 7 (round 6, second half: eagcn_head_*); bumped with every struct-layout / signature change */
+int eagcn_abi_version(void);           /* 8 (eagcn_layer_route); bumped with every struct-layout / signature change */
 size_t eagcn_struct_size(int which);   /* 0 batch, 1 layout, 2 layer_params, 3 layer_bufs, 4 layer_grads,
                                           5 head_params, 6 head_grads, 7 model, 8 gat_params, 9 pool_att */
 const char* eagcn_last_error(void);
@@ -231,6 +231,29 @@ int eagcn_layer_fp(const eagcn_layer_params* p);       /* Fp = sum_k pad16(F_k) 
 size_t eagcn_layer_packed_bytes(const eagcn_batch* b, const eagcn_layer_params* p);
 size_t eagcn_layer_fwd_scratch_bytes(const eagcn_batch* b, const eagcn_layer_params* p);
 size_t eagcn_layer_bwd_scratch_bytes(const eagcn_batch* b, const eagcn_layer_params* p);
+/* Which kernels a layer call would run for this batch: the route the library plans once per call and then carries out, for tests
+ * and tools.  A pure host function -- no device pointer is dereferenced (addresses only count through their alignment), nothing is
+ * launched.  has_dx: d(layer input) is asked for; mol_grad: the upstream gradient comes per molecule (top layer of the model
+ * engine); input_only: the backward forms d(layer input) alone; has_drain_out: a layer below could take the edge-gradient reduction.
+ *   out[0]  forward product     0 none (no packed row) | 1 operand planes | 2 balanced fp32 kernel | 3 tiled fp32 kernel |
+ *           4 refused (x exists as plane images only and the plane product does not apply: the call fails)
+ *   out[1]  the forward splits x into planes itself     out[11] the backward does
+ *   out[2]  forward aggregation 0 matrix-core kernels | 1 LDS-staged bond lists           out[3] backward aggregation, likewise
+ *   out[4]  second pass of the BatchNorm backward: 0 none | 1 elementwise, from the stored dH | 2 second pass of the reduction
+ *           kernel | staged by the LDS-staged aggregation: 3 from the stored dH | 4 from the upstream gradient | 5 from the
+ *           upstream gradient and the row mask (eval-mode input-only Concate)
+ *   out[5]  the per-molecule gradient is written as rows before the reduction    out[6] ... after it (never both)
+ *   out[7]  the reduction stores dH
+ *   out[8]  edge gradients      0 none | 1 inside the LDS-staged aggregation | 2 one grid with the aggregation | 3 own launch
+ *   out[9]  ... leave through the shared fp64 accumulators
+ *   out[10] backward products   0 none | planes: 1 dX with dW | 2 dW alone | 3 dX alone | balanced pair: 4 XCD-local slabs |
+ *           5 dW scattered in place | tiled: 6 pair | 7 separate launches | 8 dX alone | 9 refused (as out[0])
+ *   out[12] the edge-gradient reduction is left to the next layer's first backward kernel
+ *   out[13] a layer handed plane images of x alone would cope in both directions (what the model engine asks before it drops the
+ *           fp32 matrix: out[0] == 1 and out[10] == 1 of a call with has_dx that brings x_planes)
+ *   out[14], out[15] 0 */
+int eagcn_layer_route(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, int has_dx, int mol_grad,
+                      int input_only, int has_drain_out, int32_t out[16]);
 
 /* ---- batch index ----------------------------------------------------------------------------- */
 /* stage 1: needs code, deg_bn, nat, row0, tile0, meta; copies meta to host_meta (pinned) async */

@@ -65,7 +65,7 @@ def test_attr_symbols_exported():
     for name in NEW_SYMBOLS:
         assert hasattr(lib, name), name
         assert name in L.SIGNATURES, name
-    assert lib.eagcn_abi_version() == 7
+    assert lib.eagcn_abi_version() == 8
 
 
 def test_backward_input_argument_checks_without_gpu():

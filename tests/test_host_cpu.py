@@ -30,7 +30,7 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), 'libeagcn_hip.so does not export %s' % name
     assert set(declared) == set(_lib.SIGNATURES), set(declared) ^ set(_lib.SIGNATURES)
-    assert lib.eagcn_abi_version() == _lib.ABI_VERSION == 7
+    assert lib.eagcn_abi_version() == _lib.ABI_VERSION == 8
     assert lib.eagcn_pad16(140) == 144 and lib.eagcn_pad16(80) == 80
 
 
@@ -353,6 +353,23 @@ assert got == [1, 1, 1, 1, 1, 0, 1, 1, 0], got
                           .replace("assert got == [1, 1, 1, 1, 1, 0, 1, 1, 0], got", "assert got == [1, 1, 0, 1, 1, 0, 1, 1, 0], got")],
                          capture_output=True, text=True, cwd=str(ROOT))
     assert off.returncode == 0, off.stdout + off.stderr
+
+
+@pytest.mark.parametrize('switches', [{}, {'EAGCN_LAGG_WFUSE': '0'}, {'EAGCN_BWD_STORE_DH': '1'}, {'EAGCN_AGG': 'dense'},
+                                      {'EAGCN_NO_GEMM3': '1'}, {'EAGCN_GEMM_X6': '0'}, {'EAGCN_GEMM_X6': '0', 'EAGCN_NO_GEMM3': '1'}],
+                         ids=lambda s: ','.join('%s=%s' % kv for kv in s.items()) or 'default')
+def test_layer_routes_by_batch_layer_and_call(switches):
+    """eagcn_layer_route (csrc/layer.hip plan_layer: which kernels a layer call runs, decided once) against the routes written out
+    in tests/route_check.py: structure x batch shape x layer kind x per-molecule gradient x training x input-only x auxiliary
+    stream, the invariants of every route and -- with no switch set -- the pinned byte counts of the three carvings.  The plain
+    fp32 mode (EAGCN_GEMM_X6=0) is what reaches the balanced kernels EAGCN_NO_GEMM3 turns off.  In a subprocess: the library
+    reads its switches once."""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if not k.startswith('EAGCN_')}
+    env.update(switches)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'route_check.py')], capture_output=True, text=True, cwd=str(ROOT), env=env)
+    assert r.returncode == 0 and 'routes checked: 672' in r.stdout, r.stdout + r.stderr
 
 
 def test_bond_list_buffers_are_laid_out_without_overlap():
