@@ -106,6 +106,7 @@ struct ModelSaved {
     float* padc;                 // [B][ldo]
     uint32_t* pad_tab;           // [(N + 1)^2] binomial thresholds of the non-stored rows' kept counts (readout.hip), or unused
     size_t xout_last_off, pad_last_off;
+    float *top_a1, *top_a2;      // [B][f_in] per-molecule sums of the fused read-out for the top layer's BatchNorm backward (ReadoutBn.A1 / A2)
 };
 // the last layer's non-stored rows go through a SAMPLED dropout when they reach the read-out unmasked
 static bool pad_sampled(const eagcn_model* m) {
@@ -155,6 +156,9 @@ static size_t carve_saved(void* base, const eagcn_batch* b, const eagcn_model* m
         const size_t nt = (size_t)(b->N + 1) * (b->N + 1);
         s.pad_tab = c.take<uint32_t>(need ? nt : 1);
     }
+    // (behind everything else: the offsets of the pieces above do not depend on whether these are formed)
+    s.top_a1 = c.take<float>(B * h->f_in);
+    s.top_a2 = c.take<float>(B * h->f_in);
     if (out) *out = s;
     return c.off;
 }
@@ -167,6 +171,9 @@ struct ModelScratch {
     double* hsb;                 // ... and backward.  Both are cleared by the forward's parameter-packing launch; the backward clears
                                  // its own again on the way out (bn_bwd_reduce of the top layer), for a second backward call
     void* layer; size_t layer_bytes;
+    float* top_dge;              // [B][f_in] dg / size: the read-out gradient as the top layer's staging gathers it (HeadTopSums.dge)
+    double* top_slab;            // [top_bn_slabs(B)][fp of the top layer][2]: sum dH, sum dH xhat over the molecules (HeadTopSums); apart
+                                 // from hst / hsb, which the top layer's finalize clears on the way
 };
 static size_t carve_scratch(void* base, const eagcn_batch* b, const eagcn_model* m, ModelScratch* out) {
     Carver2 c(base);
@@ -198,6 +205,8 @@ static size_t carve_scratch(void* base, const eagcn_batch* b, const eagcn_model*
     s.dpad = c.take<float>((size_t)EAGCN_MAX_VIEWS * ldmax);
     s.layer_bytes = lbytes;
     s.layer = c.take<char>(lbytes);
+    s.top_dge = c.take<float>(B * h->f_in);
+    s.top_slab = c.take<double>((size_t)top_bn_slabs(b->B) * eagcn_layer_fp(&m->layer[m->n_layers - 1]) * 2);
     if (out) *out = s;
     return c.off;
 }
@@ -237,6 +246,16 @@ static eagcn_layout out_layout(const eagcn_layer_params* p) {
 static bool fused_readout(const eagcn_model* m) {
     static const bool env = [] { const char* v = getenv("EAGCN_NO_FUSED_READOUT"); return !(v && v[0] == '1'); }();
     return env && m->fuse_readout && m->layer[m->n_layers - 1].structure == EAGCN_STRUCT_CONCATE;
+}
+
+// The top layer's BatchNorm backward takes its column sums from the read-out (readout.hip A1 / A2, head2.hip HeadTopSums, layer.hip
+// BN2_STAGED_FROM_READOUT) instead of a pass over its rows: a Concate top layer behind the fused read-out, sum / ave mode, training
+// with a local BatchNorm, on the route whose pass the sums replace (bond lists, N <= 256, no code books).  A pure function of the
+// model, the batch description and the switch: the forward, the head's backward and the layer's backward all ask it.
+static bool top_bn_sums(const eagcn_batch* b, const eagcn_model* m) {
+    if (!top_bn_sums_enabled() || m->n_layers < 1 || !fused_readout(m) || !m->training || m->stats_hook) return false;
+    if (m->molfp_mode != 0 && m->molfp_mode != 1) return false;
+    return layer_top_sums_route(b, &m->layer[m->n_layers - 1], m->aux_stream != nullptr);
 }
 
 // layer l's output is needed as plane images only: it has them, and the layer above reads nothing else (forward and backward)
@@ -296,10 +315,13 @@ struct HeadPlan {
     HeadGbn bg;
     double *st_g, *st_1, *st_2, *sb_g, *sb_1, *sb_2;
     bool sync;
+    const int64_t* size;         // the molecules' atom counts ('ave' read-out), for the sums HeadGbn takes on the way (HeadTopSums)
 };
 static HeadPlan head_plan(const eagcn_batch* b, const eagcn_model* m, const ModelSaved& sv, const ModelScratch& sc, float* out,
-                          float* graph_rep, const float* dout, const float* dgraph_rep, const eagcn_head_grads* hg) {
+                          float* graph_rep, const float* dout, const float* dgraph_rep, const eagcn_head_grads* hg,
+                          const int64_t* size = nullptr) {
     HeadPlan P;
+    P.size = size;
     const eagcn_head_params* h = &m->head;
     const int B = b->B, F = h->f_in, n1 = h->n_den1, n2 = h->n_den2, nc = h->nclass;
     P.st_g = sc.hst; P.st_1 = sc.hst + 2 * F + 2; P.st_2 = sc.hst + 2 * (F + n1) + 4;
@@ -350,6 +372,12 @@ static HeadPlan head_plan(const eagcn_batch* b, const eagcn_model* m, const Mode
     //  B = 1024 -- every packed row then gathers two molecule rows instead of one)
     P.bg = HeadGbn{B, F, sc.dgn, sv.g, sv.bn_g, P.sb_g, sc.dg, hg->d_gbn_w, hg->d_gbn_b, m->training};
     if (P.sync) { P.bg.cnt = cn_g; P.bg.gscale = gscale; }
+    if (top_bn_sums(b, m)) {
+        const eagcn_layer_params* last = &m->layer[m->n_layers - 1];
+        const eagcn_layout lay = out_layout(last);
+        P.bg.top = HeadTopSums{sv.top_a1, sv.top_a2, sc.top_slab, top_bn_slabs(B), eagcn_layer_fp(last), make_colmap(&lay), P.size, m->molfp_mode,
+                               top_bn_gather_enabled() ? sc.top_dge : nullptr};
+    }
     if (ks > 1) {
         P.bg.sum[0] = HeadDwSum{hg->d_den3_w, part3, n2 * nc, ks};
         P.bg.sum[1] = HeadDwSum{hg->d_den2_w, part2, n1 * n2, ks};
@@ -419,6 +447,7 @@ static int model_forward_trunk(const eagcn_batch* b, const eagcn_model* m, const
         rb.size = size; rb.mode = m->molfp_mode; rb.g = sv.g; rb.F = F; rb.st = st_g;
         rb.cnt0 = st_g + 2 * F; rb.cnt1 = st_1 + 2 * n1; rb.cnt2 = st_2 + 2 * n2;
         rb.st_copies = copies; rb.st_stride = sc.n_hst;
+        if (top_bn_sums(b, m)) { rb.A1 = sv.top_a1; rb.A2 = sv.top_a2; }
         RC(readout_bn_forward(b, &lay, rb, stream));
     } else if (pad_sampled(m))
         RC(readout_forward_sampled(b, LL.xout, &lay, last, LL.bn + (size_t)LL.fp /* shift row of the BatchNorm table */, size,
@@ -625,7 +654,7 @@ extern "C" int eagcn_model_forward_step(const eagcn_batch* b, const eagcn_model*
     ModelSaved sv;
     ModelScratch sc;
     RC(model_forward_trunk(b, m, afm, size, saved, saved_bytes, scratch, scratch_bytes, sv, sc, stream, "eagcn_model_forward_step"));
-    const HeadPlan P = head_plan(b, m, sv, sc, out, graph_rep, loss->dout, dgraph_rep, hg);
+    const HeadPlan P = head_plan(b, m, sv, sc, out, graph_rep, loss->dout, dgraph_rep, hg, size);
     const eagcn_head_params* h = &m->head;
     if (!P.sync && head_mid_ok(h->n_den2, h->nclass)) {
         // F1, F2 (counts the labelled entries on the way), then out + loss + d a2 as ONE launch, dense 3's weight gradient in
@@ -694,7 +723,7 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
     const bool weighted = last->structure == EAGCN_STRUCT_WEIGHTED;
     const bool sampled = pad_sampled(m);
     if (with_head) {
-        const HeadPlan P = head_plan(b, m, sv, sc, nullptr, nullptr, dout, dgraph_rep, hg);
+        const HeadPlan P = head_plan(b, m, sv, sc, nullptr, nullptr, dout, dgraph_rep, hg, size);
         RC(head_backward_launches(m, P, stream));
         // (the gradient of the non-stored rows only enters the BatchNorm reductions, which the input-only form skips in eval mode)
         if (!(input_only && !m->training)) RC(readout_pad_backward(b, m, size, sv, sc, stream));
@@ -729,6 +758,10 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
         o.rg = top ? &rgd : nullptr; o.dpad_views = top && sampled; o.zero_after = top ? &zb : nullptr;
         o.drain_in = pend_in.eacc ? &pend_in : nullptr; o.drain_out = (l > layer_lo && !input_only) ? &pend_out : nullptr;
         o.input_only = input_only;
+        if (top && !input_only && top_bn_sums(b, m)) {
+            o.top_sums = sc.top_slab; o.top_nslab = top_bn_slabs(b->B);
+            o.top_dge = top_bn_gather_enabled() ? sc.top_dge : nullptr;
+        }
         RC(layer_backward_impl(b, &m->layer[l], &w, top ? nullptr : cur, dpad, l > 0 ? other : dx0, input_only ? nullptr : &lg[l],
                                stream, o));
         pend_in = pend_out;

@@ -496,7 +496,9 @@ __device__ __forceinline__ void hg_body(const HeadGbn& a, int wg, int nwg) {
         const float sc = a.bn[HT_SC * a.F + f], mu = a.bn[HT_MU * a.F + f], inv = a.bn[HT_INV * a.F + f];
         const double s1 = a.sb[2 * f], s2 = a.sb[2 * f + 1];
         const float c1 = a.training ? (float)(s1 / Bn) : 0.0f, c2 = a.training ? (float)(s2 / Bn) : 0.0f;
-        a.dg[e] = sc * (a.dgn[e] - c1 - (a.g[e] - mu) * inv * c2);
+        const float dgv = sc * (a.dgn[e] - c1 - (a.g[e] - mu) * inv * c2);
+        a.dg[e] = dgv;
+        if (a.top.A1 && a.top.dge) a.top.dge[e] = a.top.mode == 1 ? dgv * (1.0f / (float)a.top.size[e / a.F]) : dgv;
         if (e < (size_t)a.F) { a.dgamma[f] = (float)(s2 * (double)a.gscale); a.dbeta[f] = (float)(s1 * (double)a.gscale); }
     }
     // weight gradients of the dense layers that left as row-chunk partials (HeadBwd.ks): summed in chunk order
@@ -510,6 +512,46 @@ __device__ __forceinline__ void hg_body(const HeadGbn& a, int wg, int nwg) {
 #pragma unroll
             for (int c = 1; c < 16; ++c) t += c < q.ks ? v[c] : 0.0f;
             q.dst[i] = t;
+        }
+    }
+    // column sums of the top layer's BatchNorm backward (HeadTopSums): a thread owns one (slab, packed column) pair and walks the
+    // slab's molecules s, s + nslab, ... eight at a time, forming dg again (same expression as above: the values other workgroups
+    // store are not visible here) -- plain stores into a few slabs, no atomics
+    if (a.top.A1) {
+        const HeadTopSums& t = a.top;
+        const int items = t.nslab * t.fp;
+        for (int it = wg * 256 + threadIdx.x; it < items; it += nwg * 256) {
+            const int sl = it / t.fp, cp = it - sl * t.fp;
+            int eo = 0, po = 0, f = -1;
+            for (int sg = 0; sg < t.map.nseg; ++sg) {
+                if (cp < po + t.map.p[sg]) { f = (cp - po < t.map.w[sg]) ? eo + (cp - po) : -1; break; }
+                eo += t.map.w[sg];
+                po += t.map.p[sg];
+            }
+            double s1 = 0.0, s2 = 0.0;
+            if (f >= 0) {
+                const float sc = a.bn[HT_SC * a.F + f], mu = a.bn[HT_MU * a.F + f], inv = a.bn[HT_INV * a.F + f];
+                const float c1 = a.training ? (float)(a.sb[2 * f] / Bn) : 0.0f, c2 = a.training ? (float)(a.sb[2 * f + 1] / Bn) : 0.0f;
+                for (int b0 = sl; b0 < a.B; b0 += 8 * t.nslab) {
+                    float dn[8], gv[8], v1[8], v2[8], is[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const int b = min(b0 + u * t.nslab, a.B - 1);
+                        const size_t e = (size_t)b * a.F + f;
+                        dn[u] = a.dgn[e]; gv[u] = a.g[e]; v1[u] = t.A1[e]; v2[u] = t.A2[e];
+                        is[u] = t.mode == 1 ? 1.0f / (float)t.size[b] : 1.0f;
+                    }
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        if (b0 + u * t.nslab < a.B) {
+                            const float d = sc * (dn[u] - c1 - (gv[u] - mu) * inv * c2) * is[u];
+                            s1 += (double)d * (double)v1[u];
+                            s2 += (double)d * (double)v2[u];
+                        }
+                    }
+                }
+            }
+            *reinterpret_cast<double2*>(t.slab + (size_t)it * 2) = make_double2(s1, s2);
         }
     }
 }

@@ -19,8 +19,12 @@ struct AggArgs {
     int xcd = 0;                 // wave-per-tile variant: tiles handed out so that an XCD works on CONTIGUOUS tiles (agg.hip)
     // input-only backward, Concate layer in eval mode (lagg_in.hip, with w_aw set): `src` is the upstream gradient at the PACKED column and
     // dH = src m_i [relu'(sc Y' + sh) > 0] (bn_bwd_reduce_kernel<false,...> with c1 = c2 = 0); w_aw is not read then.  (Here, in the
-    // padding in front of `planes`: the argument block of the other forms keeps its layout)
+    // padding in front of `planes`: the argument block of the other forms keeps its layout.)  Also the staging of lagg_top.hip: a Concate
+    // top layer in training mode whose dH is never stored, with the dropout draw and the means of the BatchNorm backward
     bool w_rowm = false;
+    // ... with the edge gradients (lagg_top.hip): `src` is the per-MOLECULE gradient [B][lds] at the EXACT column (dg / size of the
+    // read-out, HeadTopSums.dge) and a row gathers its molecule's -- no T x Fp upstream matrix exists at all
+    bool w_gather = false;
     BxOut planes = {nullptr, 0, 0, 0};   // transposed: dP leaves as bf16 planes INSTEAD of the fp32 matrix (only the plane GEMMs read it)
     // transposed, lagg.hip only: `src` holds dH (the BatchNorm's upstream gradient), not dY': the BatchNorm backward's second pass
     //     dY' = sc (dH - c1 - (Y' - mu) inv c2)      (layer.hip bn_bwd_apply_kernel)
@@ -60,6 +64,8 @@ int launch_lagg_fwd(AggArgs a, hipStream_t s);
 int launch_lagg_bwd(AggArgs a, const EdgeArgs& e, hipStream_t s, bool edge = true);
 // lagg_in.hip: the edge = false instantiations, on the grid launch_lagg_bwd computed
 int launch_lagg_bwd_input(const AggArgs& a, const EdgeArgs& e, dim3 grid, hipStream_t s);
+// lagg_top.hip: the row-mask staging WITH the edge gradients (Concate top layer whose dH is never stored), same grid
+int launch_lagg_bwd_top(const AggArgs& a, const EdgeArgs& e, dim3 grid, hipStream_t s);
 
 struct EdgeArgs {
     eagcn_batch bt;
@@ -240,9 +246,17 @@ struct HeadBwd {                 // backward of  y = act(bn_p(x)) . W : d(bn_p o
 };
 inline int head_dw_chunks(int B) { return B > 256 ? (B + 255) / 256 < 16 ? (B + 255) / 256 : 16 : 1; }
 struct HeadDwSum { float* dst; const float* part; int n, ks; };     // dst[i] = sum_c part[c * n + i]
+// the column sums of the top layer's BatchNorm backward, taken where dg is formed (layer.hip BN2_STAGED_FROM_READOUT):
+//   slab[s][cp][0..1] = sum over the molecules b = s, s + nslab, ... of dg_eff[b][c] * (A1, A2)[b][c]   (fp64; cp = packed column of c,
+//   zero at the padded columns), dg_eff = dg / size in 'ave' mode (ReadoutGrad).  A1 == null: no such job
+//   dge (optional): [B][F] dg_eff itself, for the kernels that gather it per row (lagg_top.hip)
+struct HeadTopSums { const float *A1, *A2; double* slab; int nslab, fp; ColMapD map; const int64_t* size; int mode; float* dge; };
 struct HeadGbn { int B, F; const float *dgn, *g, *bn; const double* sb; float *dg, *dgamma, *dbeta; int training;
                  const double* cnt = nullptr; float gscale = 1.0f;
-                 HeadDwSum sum[3] = {}; int nsum = 0; };            // partial weight gradients of the dense layers (HeadBwd.ks)
+                 HeadDwSum sum[3] = {}; int nsum = 0;               // partial weight gradients of the dense layers (HeadBwd.ks)
+                 HeadTopSums top = {}; };
+// slabs of those sums: a small fixed count (the finalize adds up to 64 with sixteen lanes per column), each a chain of B / count molecules
+inline int top_bn_slabs(int B) { return B > 256 ? 64 : 16; }
 // the middle of a TRAINING step's head in one launch: last forward stage, loss, dense 3's d(input) (head2.hip head_mid_kernel)
 struct HeadLoss { int kind;                 // 0: weighted BCE with logits over the labelled entries (train.py:326-331), 1: MSE (train.py:321-325)
                   const float* labels; const float* weight; float* loss; const float* scale; float* dout; };
@@ -276,7 +290,15 @@ struct LayerBwdOpts {
     const EdgeDrain* drain_in = nullptr;     // pending edge reduction of the layer above
     EdgeDrain* drain_out = nullptr;          // receives this layer's, if nothing else is left for its gradient unpacking
     bool input_only = false;                 // (below)
+    // model engine, Concate top layer behind the fused read-out: sum dH and sum dH xhat per packed column arrive as top_nslab fp64
+    // slabs [slab][fp][2] (HeadTopSums) -- the reduction pass over the rows is skipped and no dH is stored
+    const double* top_sums = nullptr; int top_nslab = 0;
+    const float* top_dge = nullptr;          // ... and dg / size per molecule [B][rg.F] (HeadTopSums.dge), or null: rows of rg are written
 };
+// would the backward of top layer p (per-molecule upstream gradient) take the route that top_sums replaces a pass of?  (layer.hip)
+bool layer_top_sums_route(const eagcn_batch* b, const eagcn_layer_params* p, bool aux_stream);
+bool top_bn_sums_enabled();                  // eagcn_set_top_bn_sums != 0
+bool top_bn_gather_enabled();                // ... == 1: the staging gathers dg per molecule (2: rows of the read-out gradient are written)
 int layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const float* dxout,
                         const float* dpad_row, float* dx, const eagcn_layer_grads* g, void* stream,
                         const LayerBwdOpts& o = LayerBwdOpts{});
@@ -313,6 +335,9 @@ struct ReadoutBn {
     int st_copies = 1, st_stride = 0;        // replicas of st (HeadFwd): workgroup x adds to replica x % st_copies
     bool pair = false;                       // set by the launcher: a lane quad shares a dropout draw
     double *cnt0, *cnt1, *cnt2;              // optional row-count slots of the head's BatchNorms (sync-BatchNorm)
+    // optional: [B][F] per-molecule sums of q and q * xhat, q = d x[r][c] / d(relu argument) = m_r * dropout scale * [sc Y' + sh > 0],
+    // xhat = (Y' - mu) inv -- what the BatchNorm backward's column sums need of the rows (HeadTopSums); null: not formed
+    float* A1 = nullptr; float* A2 = nullptr;
 };
 int readout_bn_forward(const eagcn_batch* b, const eagcn_layout* lay, const ReadoutBn& a, void* stream);
 int readout_forward_sampled(const eagcn_batch* b, const float* x, const eagcn_layout* lay, const eagcn_layer_params* p,

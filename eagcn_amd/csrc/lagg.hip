@@ -181,9 +181,12 @@ int launch_lagg_bwd(AggArgs a, const EdgeArgs& e, hipStream_t s, bool edge) {
     static const int dbgm = [] { const char* e = getenv("EAGCN_LAGG_DBG"); return e ? atoi(e) : 0; }();
     a.xcd = dbgm;
     EAGCN_CHECK_ARG(!a.w_aw || a.bn_tab, "lagg: the upstream-gradient form needs the BatchNorm tables");
-    EAGCN_CHECK_ARG(!a.w_rowm || (!edge && a.bn_tab), "lagg: the row-mask staging belongs to the input-only form");
+    EAGCN_CHECK_ARG(!a.w_rowm || a.bn_tab, "lagg: the row-mask staging needs the BatchNorm tables");
     if (!edge) {
         rc = launch_lagg_bwd_input(a, e, grid, s);                    // input-only backward (layer.hip): lagg_in.hip
+        if (rc) return rc;
+    } else if (a.w_rowm) {
+        rc = launch_lagg_bwd_top(a, e, grid, s);                      // Concate top layer without a stored dH: lagg_top.hip
         if (rc) return rc;
     } else if (a.w_aw) {
         // (one instantiation: with one chunk per workgroup the records of a block are simply built in front of its only chunk; the

@@ -1,6 +1,6 @@
 // The LDS-staged bond-list aggregation kernel (lagg.hip: the design notes, the policy and the launches of the edge-gradient forms;
-// lagg_in.hip: the launches of the input-only backward's forms, EDGE = false).  One template, instantiated in those two translation
-// units only.
+// lagg_in.hip: the launches of the input-only backward's forms, EDGE = false; lagg_top.hip: the row-mask staging with the edge
+// gradients).  One template, instantiated in those three translation units only.
 #pragma once
 
 #include "common.h"
@@ -57,13 +57,17 @@ constexpr int LG_NOVF = 32;
 // WFUSE (transposed, Weighted_sum layers): a.src is the layer's upstream gradient; dH is formed in the staging (AggArgs.w_aw)
 // EDGE = false (transposed, input-only backward of layer.hip): the transposed aggregation alone -- no P rows of the edge gradients, no
 //   row dots, no bond-type histogram and no flush into the accumulator slabs (EdgeArgs: only Y' is read, for the BatchNorm staging)
-// CROWS (with WFUSE, EDGE = false; Concate layers in eval mode): a.src is the layer's upstream gradient at the PACKED column (as wide
-//   as dH), multiplied by the row mask m_i instead of the view weight: dH = relu'(sc Y' + sh) m_i up, then dY' = sc dH (c1 = c2 = 0)
-template <bool TRANS, bool MULTI, bool WFUSE = false, bool EDGE = true, bool CROWS = false>
+// CROWS (with WFUSE; Concate layers): a.src is the layer's upstream gradient at the PACKED column (as wide as dH), multiplied by the
+//   row mask m_i instead of the view weight: dH = relu'(sc Y' + sh) m_i keep up / (1 - p).  EDGE = false: eval mode, dY' = sc dH
+//   (c1 = c2 = 0); EDGE = true (lagg_top.hip): a top layer in training mode whose BatchNorm means came from the read-out's sums
+// GATHER (with CROWS and EDGE): a.src is that gradient per MOLECULE, [B][a.lds] at the EXACT column (AggArgs.w_gather): a row loads its
+//   molecule's four columns (the molecule of a row is in LDS since barrier R2; view widths are multiples of four there)
+template <bool TRANS, bool MULTI, bool WFUSE = false, bool EDGE = true, bool CROWS = false, bool GATHER = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void lagg_kernel(AggArgs a, EdgeArgs ed) {
     static_assert(TRANS || !WFUSE, "the upstream-gradient form belongs to the transposed kernel");
     static_assert(TRANS || EDGE, "the forward has no edge gradients to drop");
-    static_assert(!CROWS || (WFUSE && !EDGE), "the row-mask staging is a form of the input-only kernel");
+    static_assert(!CROWS || WFUSE, "the row-mask staging is a form of the upstream-gradient staging");
+    static_assert(!GATHER || (CROWS && EDGE && MULTI), "the per-molecule gather is a form of the row-mask staging with the edge gradients");
     constexpr bool TE = TRANS && EDGE;               // transposed WITH the edge gradients
     constexpr int NREC = TRANS ? 3 : 2;
     __shared__ float4 buf[LAGG_RB][LG_LPR];          // the block's operand rows x this chunk's columns (32 KB)
@@ -104,6 +108,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
     int g = tid / LG_LPR;                                             // (row group; re-declared opaque per block below)
     int col, c0, c0s;                                                 // this lane's first column inside the view / the matrix, per chunk
     bool col_ok;
+    int ex0 = 0;                                                      // GATHER: first exact column of the view
+    if constexpr (GATHER) {
+#pragma unroll
+        for (int v = 0; v < EAGCN_MAX_VIEWS; ++v) ex0 += v < k ? a.vc.width[v] : 0;
+    }
     auto set_chunk = [&](int cc) __attribute__((always_inline)) {
         col = cc * LG_CW + 4 * l;
         col_ok = col < wk;
@@ -327,13 +336,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
         //      Every load is unconditional on a clamped address (a load under a per-lane condition compiles to a branch and, behind it,
         //      a wait per load); what a lane must not use is zeroed afterwards.
         float4 v[LG_U], yv[TRANS ? LG_U : 1];
-        float rmv[CROWS ? LG_U : 1];
+        float rmv[(CROWS && !EDGE) ? LG_U : 1];
+        // GATHER: this lane's exact column (the view's first beyond the exact width), from c0s: nothing more is held across the chunk
+        int ce = 0;
+        if constexpr (GATHER) { const int cx = c0s - a.vc.off[k]; ce = ex0 + (cx < a.vc.width[k] ? cx : 0); }
 #pragma unroll
         for (int u = 0; u < LG_U; ++u) {
             const int rc = min(g + LG_G * u, rows - 1);
-            v[u] = *reinterpret_cast<const float4*>(a.src + (size_t)(R0 + rc) * a.lds + ((WFUSE && !CROWS) ? (col_ok ? col : 0) : c0s));
+            // (a 32-bit element offset on the uniform base: one address register per load; B x F floats are far below 2^32 bytes)
+            if constexpr (GATHER) v[u] = *reinterpret_cast<const float4*>(a.src + ((uint32_t)(m0 + s_rm[rc]) * (uint32_t)a.lds + (uint32_t)ce));
+            else v[u] = *reinterpret_cast<const float4*>(a.src + (size_t)(R0 + rc) * a.lds + ((WFUSE && !CROWS) ? (col_ok ? col : 0) : c0s));
             if constexpr (TRANS) yv[u] = *reinterpret_cast<const float4*>(ed.Y + (size_t)(R0 + rc) * ed.ld + c0s);
-            if constexpr (CROWS) rmv[u] = bt.row_m[R0 + rc];
+            if constexpr (CROWS && !EDGE) rmv[u] = bt.row_m[R0 + rc];
         }
         if constexpr (!MULTI) {
             hdr_loads();
@@ -378,6 +392,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
                         // per component put the LDS reads under exec-mask branches)
                         int lq = l;
                         asm volatile("" : "+v"(lq));
+                        if constexpr (GATHER) {                       // (padded columns of the view: no upstream)
+                            if (c0s - a.vc.off[k] >= a.vc.width[k]) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                        }
                         uint32_t mb;
                         {
                             const float4 bA = s_bn[0][lq], sh = s_bn[3][lq];
@@ -388,7 +405,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
                         asm volatile("" : "+v"(mb));
                         {
                             const float ik = a.w_drop ? a.w_inv_keep : 1.0f;
-                            const float wm = CROWS ? rmv[u] : w_ave;  // (Concate: the row mask, as bn_bwd_reduce_kernel<false, ...> applies it)
+                            // (Concate: the row mask, as bn_bwd_reduce_kernel<false, ...> applies it.  With the edge gradients there are no
+                            //  eight registers to hold it across the loads: m_i is 0 or 1 and s_i = m_i / rowsum_i is in LDS since barrier R2)
+                            float wm = w_ave;
+                            if constexpr (CROWS && !EDGE) wm = rmv[u];
+                            if constexpr (CROWS && EDGE) wm = s_rs[rr] > 0.0f ? 1.0f : 0.0f;
                             v[u].x = (v[u].x * wm) * ((mb & 1u) ? ik : 0.0f);
                             v[u].y = (v[u].y * wm) * ((mb & 2u) ? ik : 0.0f);
                             v[u].z = (v[u].z * wm) * ((mb & 4u) ? ik : 0.0f);
@@ -702,8 +723,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
         __syncthreads();
         // non-zero bins -> one of the shared accumulator slabs (kernels.h EDGE_COPIES; drained by unpack_grads)
         double* out = ed.datt + ((size_t)((blockIdx.y + blockIdx.x) & (EDGE_COPIES - 1)) * ed.vc.K + k) * EDGE_SLAB;
-        const double hv = h_s[tid];
-        if (hv != 0.0) atomicAdd(&out[tid], hv);
+        int te = tid;
+        if constexpr (GATHER) asm volatile("" : "+v"(te));           // (else the LDS address of h_s[tid] is kept from the prologue: one spilled register)
+        const double hv = h_s[te];
+        if (hv != 0.0) atomicAdd(&out[te], hv);
         if (tid == 0 && h_s[256] != 0.0) atomicAdd(&out[256], h_s[256]);
     }
 }

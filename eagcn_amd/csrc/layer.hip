@@ -577,13 +577,15 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const double* __re
                                                                const float* __restrict__ bn, ViewCols vc,
                                                                GradPtrs gp, float* __restrict__ cc, const int32_t* __restrict__ meta, int nvirt,
                                                                int batch_B, int da_chunks, int da_stride,
-                                                               const double* __restrict__ gsum, double* __restrict__ zero, int nzero) {
+                                                               const double* __restrict__ gsum, double* __restrict__ zero, int nzero,
+                                                               int exact_slabs) {
     // fp64 words cleared on the way (the head's backward sums, for the next backward call; every reader -- the reduction in
     // front of this launch reads Graph_BN's sums -- is done by now)
     if (blockIdx.x == 0 && zero)
         for (int i = threadIdx.x; i < nzero; i += blockDim.x) zero[i] = 0.0;
     if (meta[EAGCN_META_NLOG] > 0) M = (double)batch_B * (double)meta[EAGCN_META_NLOG];
-    nslab = max(1, min(nslab, (meta[EAGCN_META_T] + nvirt + BWD_ROWS - 1) / BWD_ROWS));   // slabs actually written
+    // slabs actually written (exact_slabs: they do not come from the row pass -- HeadTopSums writes every one whatever the row count)
+    if (!exact_slabs) nslab = max(1, min(nslab, (meta[EAGCN_META_T] + nvirt + BWD_ROWS - 1) / BWD_ROWS));
     const int cpr = blockIdx.x * (256 / L) + threadIdx.x / L, sl = threadIdx.x % L;
     const int cp = min(cpr, fp - 1);
     if (blockIdx.x == 0 && gp.dave_w) {                 // d ave.weight: 32 lanes per view over the row-partial slabs
@@ -999,7 +1001,10 @@ enum Bn2 {
                                  // no write and read of T x Fp floats, HIV 9.74 -> 9.53 ms per step)
     BN2_STAGED_FROM_DH,          // lagg.hip, while it stages the rows of the stored dH (it is the only consumer of dY')
     BN2_STAGED_FROM_UPSTREAM,    // lagg.hip re-forms dH AND dY' from the layer's upstream gradient: neither exists in memory
-    BN2_STAGED_ROWMASK           // ... of a Concate layer in eval mode (input-only form: dH = upstream x row mask x relu')
+    BN2_STAGED_ROWMASK,          // ... of a Concate layer in eval mode (input-only form: dH = upstream x row mask x relu')
+    BN2_STAGED_FROM_READOUT      // ... of a Concate top layer in training mode whose column sums came from the read-out (LayerBwdOpts.top_sums):
+                                 // no reduction pass, no stored dH; lagg_top.hip re-forms dH from the read-out gradient, gathered per
+                                 // molecule (LayerBwdOpts.top_dge) or written out as rows first (rows_late)
 };
 enum EdgePath { EDGE_NONE = 0, EDGE_WITH_LAGG, EDGE_COLAUNCH, EDGE_SEPARATE };   // lagg.hip's gathers | one grid with agg.hip | own launch
 enum BwdProd {
@@ -1013,6 +1018,8 @@ struct PlanAsk {
     bool mol_grad;               // the upstream gradient comes per molecule (ReadoutGrad)
     bool input_only;
     bool has_drain_out;          // a layer below could take this layer's edge-gradient reduction
+    bool top_sums = false;       // the BatchNorm backward's column sums are given (LayerBwdOpts.top_sums; the model engine alone asks)
+    bool top_gather = false;     // ... and the read-out gradient per molecule in a form the staging can gather (LayerBwdOpts.top_dge)
 };
 struct LayerRoute {
     FwdProd fwd_prod = FWD_NONE; bool fwd_split_x = false;      // split: the planes of x are produced here (launch_bx3_split)
@@ -1102,6 +1109,13 @@ static LayerRoute plan_layer(const eagcn_batch* b, const eagcn_layer_params* p, 
         r.rows_late = ask.mol_grad && !r.rows_first;
     } else if (bn_bwd_two_pass(wt)) r.bn2 = BN2_REDUCE_APPLY;
     else r.bn2 = (lagg && sw_lagg_fuses_bn()) ? BN2_STAGED_FROM_DH : BN2_ELEMENTWISE;
+    if (ask.top_sums && r.bn2 == BN2_STAGED_FROM_DH && ask.mol_grad && !wt) {
+        // the sums are there already; the staging gathers the read-out gradient per molecule, or reads it as rows (as wide as dH,
+        // never dH itself) written behind the finalize
+        r.bn2 = BN2_STAGED_FROM_READOUT;
+        r.rows_late = !ask.top_gather;
+        r.store_dh = false;
+    }
 
     const bool planes = d.np && !forked && bx3_ok(bq.bw) && (!ask.has_dx || bx3_ok(bq.bx));
     r.bwd_split_x = planes && !w->x_planes && !ask.input_only;
@@ -1305,6 +1319,28 @@ bool eagcn::layer_reads_planes_only(const eagcn_batch* b, const eagcn_layer_para
     return r.fwd_prod == FWD_PLANES && r.bwd_prod == BWD_PLANES_PAIR;
 }
 
+// EAGCN_TOP_BN_SUMS=0 in the environment / eagcn_set_top_bn_sums(0): the top layer's BatchNorm backward keeps its reduction pass
+static int g_top_bn_sums = env_is("EAGCN_TOP_BN_SUMS", '0') ? 0 : env_is("EAGCN_TOP_BN_SUMS", '2') ? 2 : 1;
+bool eagcn::top_bn_sums_enabled() { return g_top_bn_sums != 0; }
+bool eagcn::top_bn_gather_enabled() { return g_top_bn_sums == 1; }
+extern "C" int eagcn_set_top_bn_sums(int on) {
+    const int old = g_top_bn_sums;
+    g_top_bn_sums = on == 2 ? 2 : on ? 1 : 0;
+    return old;
+}
+// the backward of top layer p, given a per-molecule upstream gradient, would store dH in its reduction pass and leave the second pass
+// to lagg.hip: the one route whose reduction pass the read-out's sums replace (asked by the model engine before it forms them)
+bool eagcn::layer_top_sums_route(const eagcn_batch* b, const eagcn_layer_params* p, bool aux_stream) {
+    if (!b || !p || b->T <= 0 || p->structure != EAGCN_STRUCT_CONCATE || !p->training) return false;
+    void* const some = reinterpret_cast<void*>(static_cast<uintptr_t>(4096));
+    eagcn_layer_bufs w;
+    memset(&w, 0, sizeof(w));
+    w.x_planes = static_cast<const uint16_t*>(some); w.x = static_cast<const float*>(some); w.P = static_cast<float*>(some); w.scratch = some;
+    w.aux_stream = aux_stream ? some : nullptr;
+    const LayerRoute r = plan_layer(b, p, &w, layer_dims(b, p), PlanAsk{true, true, false, false, true});
+    return r.bn2 == BN2_STAGED_FROM_READOUT && r.bwd_agg == AGG_LAGG && r.edge == EDGE_WITH_LAGG;
+}
+
 int eagcn::layer_apply_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, void* stream) {
     EAGCN_CHECK_ARG(b && p && w && w->bn && w->xout && w->pad_row && w->packed, "layer_apply: null buffer");
     const LayerDims d = layer_dims(b, p);
@@ -1401,6 +1437,15 @@ static int bwd_batchnorm(LayerBwd& c) {
     }
     ProfScope ps(PROF_BN, s);
     const double M = (double)b->B * (double)b->N;
+    if (r.bn2 == BN2_STAGED_FROM_READOUT) {
+        // sum dH and sum dH xhat were taken over the molecules where dg was formed (head2.hip HeadTopSums): no pass over the rows;
+        // the finalize adds up those slabs (all of them, whatever the row count) and clears the head's sums on the way as ever
+        const int ns = c.o.top_nslab;
+        EAGCN_BY_SLABS(ns, bn_bwd_finalize_kernel, c.o.top_sums, sc.slab_da, ns, d.fp, M, p->training, w->bn, d.vc, c.gp, sc.cc, b->meta, 0,
+                       b->B, ny, ns, nullptr, ba.zero, ba.nzero, 1);
+        EAGCN_LAUNCH_CHECK();
+        return r.rows_late ? launch_readout_bwd_rows(b, ba.rg, d.ldo, sc.dY, s) : EAGCN_OK;
+    }
     const int gxb = std::max(1, std::min(b->T + ba.nvirt, d.gxb));
     bool dg = c.dg;
     if (r.rows_first) {
@@ -1423,7 +1468,7 @@ static int bwd_batchnorm(LayerBwd& c) {
         gsum = sc.gsum;
     }
     EAGCN_BY_SLABS(gxb, bn_bwd_finalize_kernel, sc.slab, sc.slab_da, gxb, d.fp, M, p->training, w->bn, d.vc, c.gp, sc.cc, b->meta, ba.nvirt,
-                   b->B, ny, gxb, gsum, ba.zero, ba.nzero);
+                   b->B, ny, gxb, gsum, ba.zero, ba.nzero, 0);
     EAGCN_LAUNCH_CHECK();
     if (r.rows_late) { rc = launch_readout_bwd_rows(b, ba.rg, d.ldo, sc.dY, s); if (rc) return rc; }
     if (r.bn2 == BN2_REDUCE_APPLY) launch_bn_bwd_pass(true, c.wt, c.dg, dr, grid2, ba, s);       // dH formed again, dY' written
@@ -1445,10 +1490,12 @@ static int bwd_aggregate(LayerBwd& c) {
     if (r.bn2_staged()) {        // lagg.hip forms dY' while it stages its rows (eval mode: zero means, no table of them)
         a.bn_tab = w->bn; a.bn_cc = (c.o.input_only && !c.p->training) ? nullptr : sc.cc; a.bn_fp = d.fp;
     }
-    if (r.bn2 == BN2_STAGED_FROM_UPSTREAM || r.bn2 == BN2_STAGED_ROWMASK) {      // ... and dH before it, from the upstream gradient
+    if (r.bn2 == BN2_STAGED_FROM_UPSTREAM || r.bn2 == BN2_STAGED_ROWMASK || r.bn2 == BN2_STAGED_FROM_READOUT) {
+        // ... and dH before it, from the upstream gradient
         a.src = c.dg ? sc.dY : c.dxout; a.lds = d.ldo;
         a.w_aw = sc.pk.colp + (size_t)CP_AVEW * d.fp;
-        a.w_rowm = r.bn2 == BN2_STAGED_ROWMASK;
+        a.w_rowm = r.bn2 != BN2_STAGED_FROM_UPSTREAM;
+        if (r.bn2 == BN2_STAGED_FROM_READOUT && !r.rows_late) { a.src = c.o.top_dge; a.lds = c.o.rg->F; a.w_gather = true; }
         agg_set_drop(a, c.drop);
     }
     EdgeArgs e;
@@ -1572,7 +1619,16 @@ int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p
     c.gemm_work = layer_gemm_work(b, p, d);
     if (!w->packed) launch_pack_params(c.pp, d, c.in, c.sc.pk, c.s);
     EAGCN_LAUNCH_CHECK();
-    c.r = plan_layer(b, p, w, d, PlanAsk{dx != nullptr, c.dg, o.input_only, o.drain_out != nullptr});
+    EAGCN_CHECK_ARG(!o.top_sums || (o.top_nslab >= 1 && c.dg && !o.input_only && !o.drain_in && p->training && !w->stats_hook),
+                    "eagcn_layer_backward: column sums from the read-out belong to a top layer in training mode with a local BatchNorm");
+    // the staging gathers four adjacent exact columns of a molecule's gradient with one 16-byte load
+    bool gather = o.top_sums && o.top_dge && (reinterpret_cast<uintptr_t>(o.top_dge) & 15) == 0 && o.rg && (o.rg->F & 3) == 0;
+    for (int k = 0; k < p->K; ++k) gather = gather && (p->width[k] & 3) == 0;
+    c.r = plan_layer(b, p, w, d, PlanAsk{dx != nullptr, c.dg, o.input_only, o.drain_out != nullptr, o.top_sums != nullptr, gather});
+    if (o.top_sums && c.r.bn2 != BN2_STAGED_FROM_READOUT) {
+        set_error("eagcn_layer_backward: column sums from the read-out were given, but the layer's route has no use for them");
+        return EAGCN_ERR_ARG;
+    }
 
     rc = bwd_batchnorm(c);
     if (rc) return rc;

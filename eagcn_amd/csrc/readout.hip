@@ -198,11 +198,17 @@ __global__ __launch_bounds__(256) void readout_fwd_kernel(eagcn_batch bt, const 
 // top layer's [T, F] output become one.  The output matrix itself is only built when somebody asks for the atom
 // representations (eagcn_model_atom_rep_materialize).
 // grid (ceil(B/4), ceil(F/64)): one WAVE per molecule, 64 lanes = 64 exact columns, four rows in flight.
+// SUMS: the rows are also summed as the top layer's BatchNorm backward needs them (ReadoutBn.A1 / A2): with the upstream gradient
+// constant over a molecule's rows, dH[r][c] = dg_eff[b][c] q[r][c], the column sums of dH and dH xhat are sums over the MOLECULES of
+// dg_eff times A1 = sum_r q and A2 = sum_r q xhat -- q and xhat formed with the expressions of layer.hip bn_bwd_reduce_kernel (same
+// relu test, same draw, same mask), per-wave fp32 partials per molecule like g.  SUMS = false is the kernel without them.
+template <bool SUMS>
 __global__ __launch_bounds__(256) void readout_bn_fwd_kernel(eagcn_batch bt, ColMapD m, ReadoutBn a) {
     // One workgroup per FOUR consecutive molecules: their packed rows are contiguous, and the four waves take them round-robin
     // (eight rows in flight per wave) whatever molecule they belong to -- a 132-atom molecule next to three 16-atom ones costs
     // every wave a quarter of the rows instead of one wave all 132.  Each wave keeps one partial sum per molecule.
     __shared__ float part[4][4][64];
+    __shared__ float part_a[SUMS ? 2 : 1][SUMS ? 4 : 1][SUMS ? 4 : 1][SUMS ? 64 : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b0 = blockIdx.x * 4;
     const int f = blockIdx.y * 64 + lane;
@@ -215,6 +221,11 @@ __global__ __launch_bounds__(256) void readout_bn_fwd_kernel(eagcn_batch bt, Col
     const bool okf = f < a.F;
     const int cp = okf ? exact_to_packed(m, f) : 0;
     float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    float a1[SUMS ? 4 : 1] = {0.0f}, a2[SUMS ? 4 : 1] = {0.0f};
+    if constexpr (SUMS) {
+#pragma unroll
+        for (int j = 1; j < 4; ++j) { a1[j] = 0.0f; a2[j] = 0.0f; }
+    }
     const int rbeg = bt.row0[b0], rend = bt.row0[b0 + nb];
     int bnd[4];                                            // first row of the next molecule, per molecule of the group
 #pragma unroll
@@ -222,6 +233,7 @@ __global__ __launch_bounds__(256) void readout_bn_fwd_kernel(eagcn_batch bt, Col
     if (okf) {
         const uint64_t seed = a.do_drop ? (a.seed_dev ? *a.seed_dev : a.seed) : 0ull;
         const float sc = a.bn[BN_SC * a.fp + cp], sh = a.bn[BN_SH * a.fp + cp];
+        const float mu = SUMS ? a.bn[BN_MU * a.fp + cp] : 0.0f, iv = SUMS ? a.bn[BN_INV * a.fp + cp] : 0.0f;
         for (int r0 = rbeg + wave; r0 < rend; r0 += 32) {
             float y[8], mk[8];
 #pragma unroll
@@ -271,12 +283,24 @@ __global__ __launch_bounds__(256) void readout_bn_fwd_kernel(eagcn_batch bt, Col
                     const int mi = (r >= bnd[0] ? 1 : 0) + (r >= bnd[1] ? 1 : 0) + (r >= bnd[2] ? 1 : 0);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) s[j] += mi == j ? v : 0.0f;
+                    if constexpr (SUMS) {
+                        // q = dH / upstream as bn_bwd_reduce_kernel forms dH = (up m) ds [h > 0] (m is 0 or 1); xhat likewise
+                        const float h = y[u] * sc + sh;
+                        const float q = h > 0.0f ? mk[u] * (a.do_drop ? ds[u] : 1.0f) : 0.0f;
+                        const float qx = q * ((y[u] - mu) * iv);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) { a1[j] += mi == j ? q : 0.0f; a2[j] += mi == j ? qx : 0.0f; }
+                    }
                 }
             }
         }
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) part[wave][j][lane] = s[j];
+    if constexpr (SUMS) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { part_a[0][wave][j][lane] = a1[j]; part_a[1][wave][j][lane] = a2[j]; }
+    }
     __syncthreads();
     if (wave == 0 && okf) {
         // (non-stored rows of a Concate layer are masked to zero: nothing to add for them)
@@ -287,6 +311,10 @@ __global__ __launch_bounds__(256) void readout_bn_fwd_kernel(eagcn_batch bt, Col
                 float v = (part[0][j][lane] + part[1][j][lane]) + (part[2][j][lane] + part[3][j][lane]);
                 if (a.mode == 1) v *= 1.0f / (float)a.size[b0 + j];
                 a.g[(size_t)(b0 + j) * a.F + f] = v;
+                if constexpr (SUMS) {
+                    a.A1[(size_t)(b0 + j) * a.F + f] = (part_a[0][0][j][lane] + part_a[0][1][j][lane]) + (part_a[0][2][j][lane] + part_a[0][3][j][lane]);
+                    a.A2[(size_t)(b0 + j) * a.F + f] = (part_a[1][0][j][lane] + part_a[1][1][j][lane]) + (part_a[1][2][j][lane] + part_a[1][3][j][lane]);
+                }
                 s1 += (double)v;
                 s2 += (double)v * (double)v;
             }
@@ -303,7 +331,10 @@ int readout_bn_forward(const eagcn_batch* b, const eagcn_layout* lay, const Read
     // lanes 4i .. 4i+3 hold the four fields of one dropout draw when every column range starts and ends on a multiple of four
     aa.pair = (a.fp & 3) == 0 && (a.F & 3) == 0;
     for (int sg = 0; sg < lay->nseg; ++sg) aa.pair = aa.pair && (lay->width[sg] & 3) == 0 && (lay->pad[sg] & 3) == 0;
-    readout_bn_fwd_kernel<<<dim3(cdiv(b->B, 4), cdiv(a.F, 64)), 256, 0, s>>>(*b, make_colmap(lay), aa);
+    EAGCN_CHECK_ARG((a.A1 == nullptr) == (a.A2 == nullptr), "readout_bn_forward: A1 and A2 come together");
+    const dim3 grid(cdiv(b->B, 4), cdiv(a.F, 64));
+    if (a.A1) readout_bn_fwd_kernel<true><<<grid, 256, 0, s>>>(*b, make_colmap(lay), aa);
+    else readout_bn_fwd_kernel<false><<<grid, 256, 0, s>>>(*b, make_colmap(lay), aa);
     EAGCN_LAUNCH_CHECK();
     return EAGCN_OK;
 }

@@ -587,6 +587,13 @@ int eagcn_bx3_used_splits(int splits, int M, int N, int K);
  * launch by its size (default; EAGCN_BX3_WIDE in the environment presets it) | 0: always the first | 1: always the second.
  * Returns the previous setting.  The used-splits queries follow the setting. */
 int eagcn_set_bx3_wide(int mode);
+/* The BatchNorm backward of a Concate top layer behind the fused read-out (model engine, training, local BatchNorm, bond-list route):
+ * 1 (default; EAGCN_TOP_BN_SUMS=0 in the environment presets 0): its column sums are taken over the molecules from two per-molecule
+ * sums of the read-out, no pass over the rows and no stored dH; the transposed aggregation gathers the read-out gradient per molecule
+ * | 2: the same, but that gradient is first written out as rows (view widths that are no multiples of four take this form anyway)
+ * | 0: the reduction pass over the rows.  Returns the previous setting.
+ * For tests and A/B runs; set it between steps (a forward and its backward must see the same value), before a graph is captured. */
+int eagcn_set_top_bn_sums(int on);
 /* ... of the TN problem (M, N, K) of eagcn_gemm_bx3_pair: its chunks are sized against the NT problem (M0, N0, K0) of the launch */
 int eagcn_bx3_pair_used_splits(int splits, int M, int N, int K, int M0, int N0, int K0);
 int eagcn_gemm_bx3(int tn, int M, int N, int K, const uint16_t* A, size_t a_pstride, int lda, int a_rows, const uint16_t* B,
