@@ -2,7 +2,8 @@
 from .layers import (GAT, AFM_BatchNorm, Ave_multi_view, Dense, Diff_Pooling, GraphAttentionLayer,  # noqa: F401
                      GraphConv_base, GraphConv_block, GraphConv_Layer, Vanilla_GCN)
 from .models import EAGCN, Concate_GCN, Weighted_GCN, weights_init  # noqa: F401
+from .training import EvalBuffers, EvalResult, evaluate  # noqa: F401
 
 __all__ = ['EAGCN', 'Concate_GCN', 'Weighted_GCN', 'GraphConv_Layer', 'GraphConv_block', 'GraphConv_base',
            'AFM_BatchNorm', 'Ave_multi_view', 'Dense', 'Vanilla_GCN', 'GAT', 'GraphAttentionLayer', 'Diff_Pooling',
-           'weights_init']
+           'weights_init', 'EvalBuffers', 'EvalResult', 'evaluate']

@@ -315,6 +315,9 @@ SIGNATURES = {
     'eagcn_bce_loss': (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp]),
     'eagcn_mse_loss': (C.c_int, [_fp, _fp, C.c_int, _fp, _fp, _fp]),
     'eagcn_eval_append': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int64, _fp]),
+    'eagcn_eval_metrics_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int]),
+    'eagcn_eval_class_metrics': (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int, _fp, C.c_size_t, _fp, _fp]),
+    'eagcn_eval_reg_metrics': (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int, _fp, C.c_size_t, _fp, _fp]),
     'eagcn_prof_enable': (None, [C.c_int]),
     'eagcn_prof_reset': (None, []),
     'eagcn_prof_ntags': (C.c_int, []),

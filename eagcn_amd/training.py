@@ -29,6 +29,7 @@ class EvalBuffers:
         self.scores = torch.empty((self.cap, self.T), dtype=torch.float32, device=self.device)
         self.targets = torch.empty((self.cap, self.T), dtype=torch.float32, device=self.device)
         self.valid = torch.empty((self.cap, self.T), dtype=torch.uint8, device=self.device)
+        self._workspace = None                             # of metrics(): sized for `cap` rows, so it is regrown with the buffers
 
     def append(self, logits, labels):
         B = logits.shape[0]
@@ -47,6 +48,65 @@ class EvalBuffers:
 
     def views(self):
         return self.scores[:self.rows], self.targets[:self.rows], self.valid[:self.rows].bool()
+
+    def metrics(self):
+        """The metrics of the rows appended so far, computed on the device (csrc/metrics.hip: two launches on the current stream,
+        no host sync): an EvalResult, whose first accessor makes the one device-to-host copy."""
+        if self.rows < 1:
+            raise L.EagcnHipError('EvalBuffers.metrics: nothing has been appended')
+        lib = L.load()
+        if self._workspace is None:
+            nbytes = lib.eagcn_eval_metrics_workspace_bytes(self.cap, self.T)
+            self._workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        out = torch.empty((5 if self.classification else 3) * self.T + 2, dtype=torch.float64, device=self.device)
+        name = 'eagcn_eval_class_metrics' if self.classification else 'eagcn_eval_reg_metrics'
+        L.check(getattr(lib, name)(self.scores.data_ptr(), self.targets.data_ptr(), self.valid.data_ptr(), self.rows, self.T,
+                                   self._workspace.data_ptr(), self._workspace.numel(), out.data_ptr(),
+                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), name)
+        return EvalResult(out, self.T, 'class' if self.classification else 'reg')
+
+
+class EvalResult:
+    """What EvalBuffers.metrics() computed, still on the device: `values` is the fp64 vector of include/eagcn_hip.h
+    ('class': auc[T] | ap[T] | P[T] | N[T] | bad[T] | mean_auc | mean_ap, 'reg': rmse[T] | mae[T] | count[T] | rmse_all | mae_all),
+    `T` the number of tasks, `kind` 'class' or 'reg'.  The accessors read a host copy made once, by the first of them.  A task
+    without both classes has auc = ap = nan and stays out of the means (as in auc_per_task); a labelled entry with a non-finite score
+    makes every classification accessor raise (sklearn raises on such input as well) -- `values` holds nan for that task."""
+
+    def __init__(self, values, n_tasks, kind):
+        self.values, self.T, self.kind = values, int(n_tasks), kind
+        self._host = None
+
+    def _get(self, kind, what):
+        if self.kind != kind:
+            raise L.EagcnHipError('EvalResult.%s: not computed for a %s evaluation'
+                                  % (what, 'regression' if self.kind == 'reg' else 'classification'))
+        if self._host is None:
+            self._host = self.values.cpu().tolist()
+        if kind == 'class':
+            for j, bad in enumerate(self._host[4 * self.T:5 * self.T]):
+                if bad > 0:
+                    raise L.EagcnHipError('EvalResult.%s: task %d has %d labelled entries whose score is not finite' % (what, j, int(bad)))
+        return self._host
+
+    def _block(self, kind, what, k):
+        return self._get(kind, what)[k * self.T:(k + 1) * self.T]
+
+    auc = property(lambda self: self._block('class', 'auc', 0))
+    ap = property(lambda self: self._block('class', 'ap', 1))
+    n_pos = property(lambda self: [int(v) for v in self._block('class', 'n_pos', 2)])
+    n_neg = property(lambda self: [int(v) for v in self._block('class', 'n_neg', 3)])
+    mean_auc = property(lambda self: self._get('class', 'mean_auc')[5 * self.T])
+    mean_ap = property(lambda self: self._get('class', 'mean_ap')[5 * self.T + 1])
+    per_task_rmse = property(lambda self: self._block('reg', 'per_task_rmse', 0))
+    per_task_mae = property(lambda self: self._block('reg', 'per_task_mae', 1))
+    count = property(lambda self: [int(v) for v in self._block('reg', 'count', 2)])
+    rmse = property(lambda self: self._get('reg', 'rmse')[3 * self.T])
+    mae = property(lambda self: self._get('reg', 'mae')[3 * self.T + 1])
+
+    def as_reference(self):
+        """What evaluate() returns without device_metrics: (per-task AUCs, mean AUC) or the RMSE over all outputs."""
+        return (self.auc, self.mean_auc) if self.kind == 'class' else self.rmse
 
 
 def auc_per_task(scores, targets, valid):
@@ -153,10 +213,11 @@ def train_step(model, optimizer, batch, labels, task, bce_weight=None, dp_global
 
 
 @torch.no_grad()
-def evaluate(model, batches, task, n_tasks):
+def evaluate(model, batches, task, n_tasks, device_metrics=False):
     """train.py:130-211: eval-mode forward over `batches` (iterable of (batch tuple, labels); a batch tuple that starts with a
     CompactBonds is (bonds, afms, size)); classification returns (per-task AUCs, mean AUC), regression the RMSE.  The model
-    is put back into training mode afterwards, as the reference does (train.py:171, 210)."""
+    is put back into training mode afterwards, as the reference does (train.py:171, 210).  device_metrics=True: the metrics
+    (average precision and MAE among them) are computed by the HIP kernels and returned as an EvalResult, without a host sync."""
     was_training = model.training
     model.eval()
     buf = None
@@ -167,5 +228,7 @@ def evaluate(model, batches, task, n_tasks):
             buf = EvalBuffers(n_tasks, task != 'reg', out.device)
         buf.append(out, labels)
     model.train(was_training)
+    if device_metrics:
+        return buf.metrics()
     scores, targets, valid = buf.views()
     return auc_per_task(scores, targets, valid) if task != 'reg' else rmse(scores, targets)

@@ -91,10 +91,11 @@ def main():
         else:
             loss = training.train_step(model, opt, b, labels, task, bce_w)
         if step % args.print_freq == 0 or step == args.steps - 1:
-            metric = training.evaluate(model, val_set, task, T)
-            torch.cuda.synchronize()
+            # the metrics are computed on the device (csrc/metrics.hip); reading one of them is the evaluation's only host sync
+            metric = training.evaluate(model, val_set, task, T, device_metrics=True)
+            shown = 'val mean ROC-AUC %.4f  mean AP %.4f' % (metric.mean_auc, metric.mean_ap) if task == 'class' else \
+                'val RMSE %.4f  MAE %.4f' % (metric.rmse, metric.mae)
             dt = time.perf_counter() - t0
-            shown = 'val mean AUC %.4f' % metric[1] if task == 'class' else 'val RMSE %.4f' % metric
             print('step %4d  loss %.5f  %s  (%.1f molecules/s incl. evaluation; %d captured runner(s))'
                   % (step, float(loss), shown, (step + 1) * args.batch / dt, len(model._runners)))
 

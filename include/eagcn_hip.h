@@ -25,6 +25,9 @@
  *   eagcn_gemm_f32       <- Dense.forward layers.py:382-387 (x @ W), used by models.py:114-120
  *   eagcn_bce_loss / eagcn_mse_loss
  *                        <- the loss of train.py:321-331 incl. weight_tensor utils.py:653-679
+ *   eagcn_eval_append / eagcn_eval_class_metrics / eagcn_eval_reg_metrics
+ *                        <- the evaluation functions train.py:130-211 (sklearn roc_curve + auc per task, RMSE; plus
+ *                           average precision and MAE)
  *   eagcn_model_forward / eagcn_model_backward
  *                        <- EAGCN.forward models.py:96-121 end to end (layers, read-out, Graph_BN,
  *                           den1/bn_den1/relu/dropout/den2/bn_den2/relu/den3) and its autograd backward
@@ -555,6 +558,26 @@ int eagcn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_
  * scores = sigmoid(logits) (classification = 1) or the predictions (0), targets = labels, valid = label in {0,1} / 1 ---- */
 int eagcn_eval_append(const float* logits, const float* labels, int B, int T, int classification, float* scores,
                       float* targets, uint8_t* valid, int64_t row_offset, void* stream);
+
+/* ---- evaluation metrics over those buffers (train.py:156-211), on the device: two launches per call, no host read, no atomics.
+ * scores / targets / valid: the [rows][T] prefix that eagcn_eval_append filled.  An entry of a classification task is a positive
+ * where valid and target == 1, a negative where valid and target == 0, unlabelled otherwise.
+ *   eagcn_eval_class_metrics: out[5T + 2] doubles = auc[T] | ap[T] | P[T] | N[T] | bad[T] | mean_auc | mean_ap
+ *     auc = roc_curve + auc of sklearn (the Mann-Whitney statistic with average ranks, an exact integer count over 2 P N),
+ *     ap = average_precision_score, P / N = labelled positives / negatives, bad = labelled entries whose score is not finite.
+ *     A task with P == 0, N == 0 or bad > 0 has auc = ap = NaN; the means run over the other tasks (NaN if there is none).
+ *   eagcn_eval_reg_metrics: out[3T + 2] doubles = rmse[T] | mae[T] | count[T] | rmse_all | mae_all over the valid entries, the last
+ *     two over all tasks' entries together (train.py:211); NaN where nothing is valid.
+ * workspace: at least eagcn_eval_metrics_workspace_bytes(rows, T) bytes, 8-byte aligned, contents irrelevant on entry (every word
+ * that is read is written by the call before); with tiles = ceil(rows / 256) and chunks = ceil(rows / 1024) that is
+ *     T * tiles * min(chunks, 8) * (256 * 8 + 32)        (0 for rows < 1 or T < 1)
+ * -- per task, tile of 256 entries and share of the rows (at most 8 workgroups share them) two 32-bit counts per entry and one
+ * 32-byte record.  rows < 2^31 (32-bit counts), T <= 65535. */
+size_t eagcn_eval_metrics_workspace_bytes(int64_t rows, int T);
+int eagcn_eval_class_metrics(const float* scores, const float* targets, const uint8_t* valid, int64_t rows, int T, void* workspace,
+                             size_t workspace_bytes, double* out, void* stream);
+int eagcn_eval_reg_metrics(const float* scores, const float* targets, const uint8_t* valid, int64_t rows, int T, void* workspace,
+                           size_t workspace_bytes, double* out, void* stream);
 
 /* Matrix-core path of the layer products (the reference's torch.mm and its two autograd products, layers.py:40):
  *   0 = fp32 MFMA: exact fp32 products, a k-ordered fmaf chain (csrc/gemm3.hip);
