@@ -316,6 +316,10 @@ void index_scan4_kernel(const float* __restrict__ adj, RelPtrs rel, int B, int N
         if (row >= nrows) break;                         // wave-uniform
         const int b = rowb_s[wave][rr], i = rowi_s[wave][rr];
         // (a row without bonds keeps whatever its code row held: no consumer gives it weight, see index_scan_kernel)
+        // What a code row holds is defined for columns below ceil(N/16)*16 of the CALLER's padded size N (type + 1 at a bond, 0
+        // elsewhere).  With n_logical below the capacity the NIT column trips may end before the capacity's ldc: columns from
+        // ceil(N/16)*16 on then keep what an earlier batch left there.  Nothing reads them: nat <= N, and every consumer stops at
+        // the 16-column tile of the molecule's last atom (tests/index_reference.py: code_cols).
         if (deg[rr] > 0) {
 #pragma unroll
             for (int t = 0; t < NIT; ++t) {
@@ -576,7 +580,9 @@ __device__ __forceinline__ void index_blocks_body(const eagcn_batch& bt, const i
 // column lists (bonds (i,j) into column j, i ascending), each with the K per-view bond-type codes of the bond in one
 // 64-bit word.  Only bonds with both ends inside the molecule's nat rows are listed (what the dense kernels multiply,
 // agg.hip); rows without bonds have undefined code rows and are skipped.  Entries of molecule b live in
-// [edge0[b], edge0[b+1]) of both list families.
+// [edge0[b], edge0[b+1]) of both list families.  A directed bond into an atom at or beyond nat (its target has no bond of its
+// own) counts in deg_bn, ecnt and edge0 and is listed nowhere: a molecule's lists may be shorter than edge0[b+1] - edge0[b], and
+// only the ranges row_ptr / col_ptr name are defined (tests/index_reference.py says the same).
 // BITMAP: the bond positions of the molecule are first packed into an LDS bitmap ([nat][W] 32-bit words, one coalesced
 // pass over the view-0 code rows), which both list families are then read from -- walking a COLUMN of the byte map in
 // global memory is one dependent single-byte load per row (measured 256 us at the Tox21 shape).  Molecules beyond 512
