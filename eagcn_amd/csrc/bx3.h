@@ -76,6 +76,23 @@ __device__ __forceinline__ void bx_store1(const BxOut& o, int r, int c, float v)
     }
 }
 
+// Tail pass of an NT product that is the dX of a layer above a Concate layer (Y == nullptr: none).  The product's element (row, col)
+// is the upstream gradient of the layer BELOW at its packed column col.  The units store it as ever; behind its stream every compute
+// wave of the 128 x 128 kernel (gemm_bx3.hip; the 256 x 128 kernel does not carry the code and refuses such a problem) walks its
+// units again, reads its blocks back and stores that layer's dH = up m_row [sc Y' + sh > 0] keep / (1 - p) in their place -- formed
+// exactly as layer.hip bn_bwd_reduce_kernel<false, false, DROP, false> forms it -- and writes sum dH and sum dH xhat per column as fp64
+// slabs [slab][fp][2], ONE slab per 64-row block of the product (slab m0 / 64: the waves of a tile own distinct (row block, column
+// block) pairs, nobody adds to anybody's sums).  Rows at or beyond the actual row count contribute nothing; ceil(rows / 64) slabs are
+// written in full (every column below N).
+struct BxBnEpi {
+    const float* Y; int ldy;     // Y' of the layer below: [rows][ldy]
+    const float* bn; int fp;     // its BatchNorm table: rows BN_SC, BN_SH, BN_MU, BN_INV of stride fp (its packed width = N of the product)
+    const float* row_m;          // [rows] row mask
+    int do_drop; uint32_t thr; float inv_keep; uint64_t seed; const uint64_t* seed_dev;      // its dropout (common.h drop_scale4)
+    double* slab;
+};
+constexpr int BX_EPI_ROWS = 64;  // rows per slab of BxBnEpi
+
 // one product of the plane GEMM (csrc/gemm_bx3.hip)
 struct BxProb {
     BxPlanes A, B;
@@ -85,6 +102,7 @@ struct BxProb {
     const int* K_dev;            // TN: actual reduction length (packed rows)
     int tn;                      // 0: C = A[M,K] . B[N,K]^T;  1: C = A[K,M]^T . B[K,N]
     int splits; size_t slab;     // TN: k-chunk z goes to C + z * slab
+    BxBnEpi ep;                  // NT: the tail pass above (ep.Y == nullptr: none)
 };
 // k-chunk slabs a split-K (TN) product of actual reduction length K over `tiles` output tiles really writes -- shared by the
 // kernel and by whoever sums the slabs (layer.hip unpack_grads); the host sizes the slab buffer (`cap`) for a CAPACITY.

@@ -36,8 +36,10 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "bx3.h"
+#include "bx3_epi.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -217,7 +219,14 @@ __device__ __forceinline__ void bx_loader(const BxProb& p, const BxStream& st, c
 //       (c >> 2), rows 4 (c & 3) .. + 3 of the block and receives the 4 k of row c: blocks 0 / 1 = rows 0-15 / 16-31 at
 //       k 0-7, blocks 2 / 3 the same rows at k 8-15 (operand layout of the 32 x 32 x 16 MFMA)
 template <bool TN, int NP, int DBG>
-__device__ __forceinline__ void bx_compute(const BxProb& p, const BxStream& st, const int wave) {
+__device__ __forceinline__ void bx_compute(const BxProb& p, const int pidx, const BxStream& st_, const int wave) {
+    // the stream in SCALAR registers (it is uniform over the wave, but not provably: a TN stream's chunk count goes through a wave-wide
+    // minimum): with the second walk behind the k-loop it is live across the loop, in vector registers the loop does not have
+    BxStream st = st_;
+#define EAGCN_BX_S(x) x = __builtin_amdgcn_readfirstlane(x)
+    EAGCN_BX_S(st.u.tiles_m); EAGCN_BX_S(st.u.tiles_n); EAGCN_BX_S(st.u.splits); EAGCN_BX_S(st.u.kt_total); EAGCN_BX_S(st.u.kt_per); EAGCN_BX_S(st.u.n);
+    EAGCN_BX_S(st.Mx); EAGCN_BX_S(st.Kx); EAGCN_BX_S(st.first); EAGCN_BX_S(st.step); EAGCN_BX_S(st.count);
+#undef EAGCN_BX_S
     const int lane = threadIdx.x & 63;
     const int wm = wave >> 1, wn = wave & 1;
     int fa[2], fb[2], fah[2], fbh[2];                  // NT: per k16-step s; TN: per 32-column tile t (lo / hi: k-rows +0 / +4)
@@ -382,6 +391,18 @@ __device__ __forceinline__ void bx_compute(const BxProb& p, const BxStream& st, 
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                      // B_end: every wave is done with the LDS stages
+    // dX of the layer above a Concate layer (BxProb.ep): the layer below's dH takes the product's place and its column sums leave as
+    // slabs (bx3_epi.h) -- BEHIND the stream, a second walk over this wave's units that reads the stored blocks back: inside the
+    // k-loop the code cost the loop registers it does not have (an NT unit is never empty: every unit was stored above)
+    if constexpr (!TN) {
+        if (p.ep.Y) {
+            for (int j2 = 0; j2 < st.count; ++j2) {
+                const BxUnit u2 = bx_unit(p, st, j2);
+                const int m0 = u2.tm * BX_BM + wm * 64, n0 = u2.tn * BX_BN + wn * 64;
+                if (m0 < st.Mx && n0 < p.N) bx_bn_epilogue(pidx, m0, n0, st.Mx, lane);
+            }
+        }
+    }
 }
 
 // XCD x (dispatch slot b runs on XCD b % 8) owns the contiguous units [x n / 8, (x + 1) n / 8) of a problem; its workgroups take
@@ -407,6 +428,7 @@ __global__ __launch_bounds__(64 * (BX_NC + BX_NL), 2) void bx3_kernel(BxProb p0,
     // the HEAVIER units first (longest-processing-time order inside a workgroup's run): the k-chunks of a dW before the dX tiles
     for (int pass = 0; pass < (has1 ? 2 : 1); ++pass) {
         const BxProb& p = (has1 && pass == 0) ? p1 : p0;
+        const int pidx = (has1 && pass == 0) ? 1 : 0;  // (p as an index into the kernel's arguments: bx3_epi.h)
         int ou = 0, okt = 0;                           // the split-K problem of a pair sizes its chunks against the NT problem's units
         if (pair_policy && has1 && pass == 0 && p1.tn && !p0.tn) {
             const BxUnits u0 = bx_units(p0, bx_mx(p0), bx_kx(p0));
@@ -415,7 +437,7 @@ __global__ __launch_bounds__(64 * (BX_NC + BX_NL), 2) void bx3_kernel(BxProb p0,
         const BxStream st = bx_stream(p, rot, rot1, ou, okt);
         rot = rot1;
         if (wave < BX_NC) {
-            if (p.tn) bx_compute<true, NP, DBG>(p, st, wave); else bx_compute<false, NP, DBG>(p, st, wave);
+            if (p.tn) bx_compute<true, NP, DBG>(p, pidx, st, wave); else bx_compute<false, NP, DBG>(p, pidx, st, wave);
         } else {
             if constexpr (DBG != 2) {
                 if (p.tn) bx_loader<true, NP>(p, st, wave - BX_NC); else bx_loader<false, NP>(p, st, wave - BX_NC);
@@ -426,6 +448,8 @@ __global__ __launch_bounds__(64 * (BX_NC + BX_NL), 2) void bx3_kernel(BxProb p0,
         }
     }
 }
+// bx3_epi.h reads problem `pidx` as element pidx of the kernel's argument segment: the two problems are the FIRST two parameters
+static_assert(std::is_same<decltype(&bx3_kernel<3, 0>), void (*)(BxProb, BxProb, int, int)>::value, "bx3_epi.h: the kernel's arguments start with its two BxProb's");
 
 // ---- operand producers -----------------------------------------------------------------------------------------------------------
 // fp32 matrix [rows][ld] -> three bf16 planes (stand-alone conversion: C-ABI entry, tests, layer-level path; the model engine's
@@ -529,6 +553,7 @@ int launch_bx3(const BxProb& p0, const BxProb* p1, int np, hipStream_t s, double
     EAGCN_CHECK_ARG(bx3_ok(p0) && (!p1 || bx3_ok(*p1)), "bx3 gemm: operands not aligned / extents unsupported");
     EAGCN_CHECK_ARG(np == 1 || np == 3, "bx3 gemm: 1 or 3 planes");
     ProfScope ps(prof_tag, s, work);
+    EAGCN_CHECK_ARG(!wide || !(p0.ep.Y || (p1 && p1->ep.Y)), "bx3 gemm: the 256 x 128 kernel has no BatchNorm tail pass (BxProb.ep)");
     if (wide) return launch_bx3w(p0, p1, np, s);
     static const int dbg = [] { const char* e = getenv("EAGCN_BX3_DBG"); return e ? atoi(e) : 0; }();     // probes (wrong results!)
     if (np == 3 && dbg == 1) return bx3_launch_cfg<3, 1>(p0, p1, s);

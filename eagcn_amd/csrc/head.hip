@@ -174,6 +174,8 @@ struct ModelScratch {
     float* top_dge;              // [B][f_in] dg / size: the read-out gradient as the top layer's staging gathers it (HeadTopSums.dge)
     double* top_slab;            // [top_bn_slabs(B)][fp of the top layer][2]: sum dH, sum dH xhat over the molecules (HeadTopSums); apart
                                  // from hst / hsb, which the top layer's finalize clears on the way
+    double* hid_slab;            // [hidden_bn_slabs(T)][widest fp below the top layer][2]: sum dH, sum dH xhat of a hidden Concate layer,
+                                 // written by the dX product of the layer above it (bx3.h BxBnEpi), one layer at a time
 };
 static size_t carve_scratch(void* base, const eagcn_batch* b, const eagcn_model* m, ModelScratch* out) {
     Carver2 c(base);
@@ -207,6 +209,9 @@ static size_t carve_scratch(void* base, const eagcn_batch* b, const eagcn_model*
     s.layer = c.take<char>(lbytes);
     s.top_dge = c.take<float>(B * h->f_in);
     s.top_slab = c.take<double>((size_t)top_bn_slabs(b->B) * eagcn_layer_fp(&m->layer[m->n_layers - 1]) * 2);
+    int fpmax = 0;
+    for (int l = 0; l + 1 < m->n_layers; ++l) fpmax = std::max(fpmax, eagcn_layer_fp(&m->layer[l]));
+    s.hid_slab = c.take<double>(fpmax ? (size_t)hidden_bn_slabs(b->T) * fpmax * 2 : 1);
     if (out) *out = s;
     return c.off;
 }
@@ -732,6 +737,11 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
     memset(&rgd, 0, sizeof(rgd));
     rgd.dg = sc.dg; rgd.F = F; rgd.size = size; rgd.mode = m->molfp_mode; rgd.map = make_colmap(&lay);
     const int top_l = m->n_layers - 1;
+    // a hidden Concate layer's dH and BatchNorm column sums come out of the dX product of the plane-pair layer above it, when both
+    // run in this call (layer.hip layer_hidden_sums_route; training, local BatchNorm, one stream): `fused` = the layer about to run
+    // finds them in its upstream buffer and in sc.hid_slab
+    BxBnEpi below;
+    bool fused = false;
     EdgeDrain pend_in, pend_out;
     pend_in.eacc = nullptr;
     pend_out.eacc = nullptr;                                     // (the input-only form hands no edge reduction down)
@@ -762,10 +772,20 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
             o.top_sums = sc.top_slab; o.top_nslab = top_bn_slabs(b->B);
             o.top_dge = top_bn_gather_enabled() ? sc.top_dge : nullptr;
         }
+        if (fused) { o.dh_sums = sc.hid_slab; o.dh_nslab = hidden_bn_slabs(b->T); }
+        bool carried = false;
+        fused = l > layer_lo && !input_only && m->training && !m->stats_hook &&
+                layer_hidden_sums_route(b, &m->layer[l], &m->layer[l - 1], m->aux_stream != nullptr, &below);
+        if (fused) {
+            below.Y = sv.L[l - 1].Y; below.bn = sv.L[l - 1].bn; below.row_m = b->row_m; below.slab = sc.hid_slab;
+            o.below = &below; o.below_done = &carried;
+        }
         RC(layer_backward_impl(b, &m->layer[l], &w, top ? nullptr : cur, dpad, l > 0 ? other : dx0, input_only ? nullptr : &lg[l],
                                stream, o));
         pend_in = pend_out;
         if (l == layer_lo) pend_in.eacc = nullptr;
+        fused = fused && carried;                                // (the layer's real plan decides: layer.hip bwd_products)
+        EAGCN_CHECK_ARG(!fused || !pend_in.eacc, "eagcn_model_backward: a plane-pair layer handed its edge reduction down");
     }
     if (forked) RC(stream_after(s, side));                       // join: every gradient is complete on s
     return EAGCN_OK;

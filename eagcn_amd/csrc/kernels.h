@@ -294,7 +294,20 @@ struct LayerBwdOpts {
     // slabs [slab][fp][2] (HeadTopSums) -- the reduction pass over the rows is skipped and no dH is stored
     const double* top_sums = nullptr; int top_nslab = 0;
     const float* top_dge = nullptr;          // ... and dg / size per molecule [B][rg.F] (HeadTopSums.dge), or null: rows of rg are written
+    // model engine, a plane-pair layer above a Concate layer (layer_hidden_sums_route): the dX product's launch forms the layer BELOW's
+    // dH and its column sums in a tail pass (bx3.h BxBnEpi, complete but for C) ...
+    const BxBnEpi* below = nullptr;
+    bool* below_done = nullptr;              // ... set when this call's dX product really carried it (the route is planned from the real buffers:
+                                             // a call whose products do not run as the plane pair ignores `below` and the layer below keeps its pass)
+    // ... and that layer's call: dxout already holds dH, sum dH and sum dH xhat arrive as one fp64 slab [fp][2] per BX_EPI_ROWS packed
+    // rows (dh_nslab: the slab CAPACITY; the finalize counts the written ones from the device-side row count) -- no reduction pass
+    const double* dh_sums = nullptr; int dh_nslab = 0;
 };
+// would the backward of layer `up` (with d(input)) run its products as the plane pair, and that
+// of the Concate layer `low` below it store dH in a reduction pass and leave the second pass to lagg.hip -- the pass the dX units'
+// tail pass replaces (on the 128 x 128 kernel: bwd_products)?  Fills what of *ep is the layer's own (dropout, widths); the caller adds Y', the table, the mask and the slabs.
+bool layer_hidden_sums_route(const eagcn_batch* b, const eagcn_layer_params* up, const eagcn_layer_params* low, bool aux_stream, BxBnEpi* ep);
+inline int hidden_bn_slabs(int T) { return (T > 0 ? T + BX_EPI_ROWS - 1 : BX_EPI_ROWS) / BX_EPI_ROWS; }      // slab capacity for T packed rows
 // would the backward of top layer p (per-molecule upstream gradient) take the route that top_sums replaces a pass of?  (layer.hip)
 bool layer_top_sums_route(const eagcn_batch* b, const eagcn_layer_params* p, bool aux_stream);
 bool top_bn_sums_enabled();                  // eagcn_set_top_bn_sums != 0

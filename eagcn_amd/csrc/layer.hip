@@ -585,7 +585,9 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const double* __re
         for (int i = threadIdx.x; i < nzero; i += blockDim.x) zero[i] = 0.0;
     if (meta[EAGCN_META_NLOG] > 0) M = (double)batch_B * (double)meta[EAGCN_META_NLOG];
     // slabs actually written (exact_slabs: they do not come from the row pass -- HeadTopSums writes every one whatever the row count)
+    // (exact_slabs == 2: one per BX_EPI_ROWS packed rows, written by the dX product of the layer above -- bx3.h BxBnEpi; no row: no slab)
     if (!exact_slabs) nslab = max(1, min(nslab, (meta[EAGCN_META_T] + nvirt + BWD_ROWS - 1) / BWD_ROWS));
+    else if (exact_slabs == 2) nslab = min(nslab, (max(meta[EAGCN_META_T], 0) + BX_EPI_ROWS - 1) / BX_EPI_ROWS);
     const int cpr = blockIdx.x * (256 / L) + threadIdx.x / L, sl = threadIdx.x % L;
     const int cp = min(cpr, fp - 1);
     if (blockIdx.x == 0 && gp.dave_w) {                 // d ave.weight: 32 lanes per view over the row-partial slabs
@@ -1020,6 +1022,7 @@ struct PlanAsk {
     bool has_drain_out;          // a layer below could take this layer's edge-gradient reduction
     bool top_sums = false;       // the BatchNorm backward's column sums are given (LayerBwdOpts.top_sums; the model engine alone asks)
     bool top_gather = false;     // ... and the read-out gradient per molecule in a form the staging can gather (LayerBwdOpts.top_dge)
+    bool dh_given = false;       // the upstream buffer holds dH already and its column sums are given (LayerBwdOpts.dh_sums)
 };
 struct LayerRoute {
     FwdProd fwd_prod = FWD_NONE; bool fwd_split_x = false;      // split: the planes of x are produced here (launch_bx3_split)
@@ -1030,6 +1033,7 @@ struct LayerRoute {
     EdgePath edge = EDGE_NONE; bool edge_atomic = false;         // atomic: the partials leave through the shared accumulators
     BwdProd bwd_prod = BWD_NONE; bool bwd_split_x = false;
     bool defer_drain = false;                                    // the edge reduction is left to the next layer's first kernel
+    bool dh_given = false;                                       // no reduction pass: dH and its sums came from the layer above's dX product
     bool bn2_staged() const { return bn2 >= BN2_STAGED_FROM_DH; }
     bool bwd_planes() const { return bwd_prod >= BWD_PLANES_PAIR && bwd_prod <= BWD_PLANES_DX; }
 };
@@ -1117,6 +1121,9 @@ static LayerRoute plan_layer(const eagcn_batch* b, const eagcn_layer_params* p, 
         r.store_dh = false;
     }
 
+    // dH and its sums were formed by the dX product of the layer above: the one route whose pass that replaces (dH stored by the
+    // pass, the second pass in lagg.hip's staging -- which then stages from the upstream buffer)
+    r.dh_given = ask.dh_given && r.bn2 == BN2_STAGED_FROM_DH && r.store_dh && !wt && !ask.mol_grad && !ask.input_only;
     const bool planes = d.np && !forked && bx3_ok(bq.bw) && (!ask.has_dx || bx3_ok(bq.bx));
     r.bwd_split_x = planes && !w->x_planes && !ask.input_only;
     if (ask.input_only) r.bwd_prod = planes ? BWD_PLANES_DX : BWD_TILED_DX;
@@ -1328,6 +1335,39 @@ extern "C" int eagcn_set_top_bn_sums(int on) {
     g_top_bn_sums = on == 2 ? 2 : on ? 1 : 0;
     return old;
 }
+// EAGCN_HIDDEN_BN_SUMS=0 in the environment / eagcn_set_hidden_bn_sums(0): the hidden layers' BatchNorm backward keeps its reduction pass
+static int g_hidden_bn_sums = env_is("EAGCN_HIDDEN_BN_SUMS", '0') ? 0 : 1;
+static long g_hidden_bn_taken = 0;
+/* layer backward calls (captured ones count when they are captured) that took dH and its sums from the layer above, since the last reset */
+extern "C" long eagcn_hidden_bn_sums_taken(int reset) {
+    const long n = g_hidden_bn_taken;
+    if (reset) g_hidden_bn_taken = 0;
+    return n;
+}
+extern "C" int eagcn_set_hidden_bn_sums(int on) {
+    const int old = g_hidden_bn_sums;
+    g_hidden_bn_sums = on ? 1 : 0;
+    return old;
+}
+bool eagcn::layer_hidden_sums_route(const eagcn_batch* b, const eagcn_layer_params* up, const eagcn_layer_params* low, bool aux_stream, BxBnEpi* ep) {
+    if (!g_hidden_bn_sums || aux_stream || !b || !up || !low || b->T <= 0 || low->structure != EAGCN_STRUCT_CONCATE || !low->training) return false;
+    void* const some = reinterpret_cast<void*>(static_cast<uintptr_t>(4096));
+    eagcn_layer_bufs w;
+    memset(&w, 0, sizeof(w));
+    w.x_planes = static_cast<const uint16_t*>(some); w.x = static_cast<const float*>(some); w.P = static_cast<float*>(some); w.scratch = some;
+    const LayerDims du = layer_dims(b, up), dl = layer_dims(b, low);
+    if (du.ld_in != dl.fp || dl.ldo != dl.fp || hidden_bn_slabs(b->T) > dl.gxb) return false;      // (never more slabs than the pass writes)
+    const LayerRoute ru = plan_layer(b, up, &w, du, PlanAsk{true, false, false, false});
+    const LayerRoute rl = plan_layer(b, low, &w, dl, PlanAsk{true, false, false, false, false, false, true});
+    if (ru.bwd_prod != BWD_PLANES_PAIR || !rl.dh_given || rl.bwd_agg != AGG_LAGG) return false;
+    if (ep) {
+        memset(ep, 0, sizeof(*ep));
+        const DropArgs dr = drop_args(low->dropout, low->training != 0, low->seed, low->seed_dev);
+        ep->ldy = dl.fp; ep->fp = dl.fp;
+        ep->do_drop = dr.on; ep->thr = dr.thr; ep->inv_keep = dr.inv_keep; ep->seed = dr.seed; ep->seed_dev = dr.seed_dev;
+    }
+    return true;
+}
 // the backward of top layer p, given a per-molecule upstream gradient, would store dH in its reduction pass and leave the second pass
 // to lagg.hip: the one route whose reduction pass the read-out's sums replace (asked by the model engine before it forms them)
 bool eagcn::layer_top_sums_route(const eagcn_batch* b, const eagcn_layer_params* p, bool aux_stream) {
@@ -1446,6 +1486,15 @@ static int bwd_batchnorm(LayerBwd& c) {
         EAGCN_LAUNCH_CHECK();
         return r.rows_late ? launch_readout_bwd_rows(b, ba.rg, d.ldo, sc.dY, s) : EAGCN_OK;
     }
+    if (r.dh_given) {
+        ++g_hidden_bn_taken;
+        // the dX units of the layer above left dH in the upstream buffer and one slab of sums per BX_EPI_ROWS rows: no pass over the rows
+        const int ns = c.o.dh_nslab;
+        EAGCN_BY_SLABS(ns, bn_bwd_finalize_kernel, c.o.dh_sums, sc.slab_da, ns, d.fp, M, p->training, w->bn, d.vc, c.gp, sc.cc, b->meta, 0,
+                       b->B, ny, ns, nullptr, ba.zero, ba.nzero, 2);
+        EAGCN_LAUNCH_CHECK();
+        return EAGCN_OK;
+    }
     const int gxb = std::max(1, std::min(b->T + ba.nvirt, d.gxb));
     bool dg = c.dg;
     if (r.rows_first) {
@@ -1490,6 +1539,7 @@ static int bwd_aggregate(LayerBwd& c) {
     if (r.bn2_staged()) {        // lagg.hip forms dY' while it stages its rows (eval mode: zero means, no table of them)
         a.bn_tab = w->bn; a.bn_cc = (c.o.input_only && !c.p->training) ? nullptr : sc.cc; a.bn_fp = d.fp;
     }
+    if (r.dh_given) { a.src = c.dxout; a.lds = d.ldo; }          // dH as the layer above's dX product left it (Concate: ldo == fp)
     if (r.bn2 == BN2_STAGED_FROM_UPSTREAM || r.bn2 == BN2_STAGED_ROWMASK || r.bn2 == BN2_STAGED_FROM_READOUT) {
         // ... and dH before it, from the upstream gradient
         a.src = c.dg ? sc.dY : c.dxout; a.lds = d.ldo;
@@ -1527,13 +1577,24 @@ static int bwd_products(LayerBwd& c, const LayerOperands& o) {
     switch (c.r.bwd_prod) {
     case BWD_PLANES_DX: return launch_bx3(bq.bx, nullptr, d.np, s, c.gemm_work, PROF_GEMM, bx3_pick_wide(bq.bx, nullptr, b->t_hint));
     case BWD_TILED_DX: return launch_gemm(gq.gx, s);
-    case BWD_PLANES_PAIR:
+    case BWD_PLANES_PAIR: {
         c.bx_wide = bx3_pick_wide(bq.bx, &bq.bw, b->t_hint);
-        rc = launch_bx3(bq.bx, &bq.bw, d.np, s, 2.0 * c.gemm_work, PROF_GEMM_PAIR, c.bx_wide);
+        BxProb bx = bq.bx;
+        // the layer below's dH and column sums leave with dX (bx3.h BxBnEpi) -- on the 128 x 128 kernel: the 256 x 128 kernel does not
+        // carry the tail pass (with it every launch of that kernel, this route or not, ran slower: DESIGN.md section 1), its launches
+        // leave the layer below on its reduction pass
+        if (c.o.below && !c.bx_wide) {
+            EAGCN_CHECK_ARG(c.o.below->Y && c.o.below->bn && c.o.below->row_m && c.o.below->slab && c.o.below->fp == bx.N && bx.ldc == bx.N,
+                            "eagcn_layer_backward: incomplete description of the layer below");
+            bx.ep = *c.o.below;
+            if (c.o.below_done) *c.o.below_done = true;
+        }
+        rc = launch_bx3(bx, &bq.bw, d.np, s, 2.0 * c.gemm_work, PROF_GEMM_PAIR, c.bx_wide);
         c.nsplit = d.bx_splits;                       // partial slabs of dWcat: summed and scattered by unpack_grads
         c.bx_slabs = true;
         c.bx_per = bx3_pair_policy() ? std::max(1, bx3_grid() >> 3) : 0;
         return rc;
+    }
     case BWD_PLANES_DW:
         c.bx_wide = bx3_pick_wide(bq.bw, nullptr, b->t_hint);
         rc = launch_bx3(bq.bw, nullptr, d.np, s, c.gemm_work, PROF_GEMM, c.bx_wide);
@@ -1624,7 +1685,18 @@ int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p
     // the staging gathers four adjacent exact columns of a molecule's gradient with one 16-byte load
     bool gather = o.top_sums && o.top_dge && (reinterpret_cast<uintptr_t>(o.top_dge) & 15) == 0 && o.rg && (o.rg->F & 3) == 0;
     for (int k = 0; k < p->K; ++k) gather = gather && (p->width[k] & 3) == 0;
-    c.r = plan_layer(b, p, w, d, PlanAsk{dx != nullptr, c.dg, o.input_only, o.drain_out != nullptr, o.top_sums != nullptr, gather});
+    EAGCN_CHECK_ARG(!o.dh_sums || (o.dh_nslab >= hidden_bn_slabs(b->T) && dxout && !c.dg && !o.input_only && !o.drain_in && !o.zero_after &&
+                                   !dpad_row && p->training && !w->stats_hook && !w->aux_stream && !o.top_sums),
+                    "eagcn_layer_backward: dH and its column sums from the layer above belong to a hidden layer in training mode with a local BatchNorm");
+    c.r = plan_layer(b, p, w, d, PlanAsk{dx != nullptr, c.dg, o.input_only, o.drain_out != nullptr, o.top_sums != nullptr, gather, o.dh_sums != nullptr});
+    if (o.below_done) *o.below_done = false;
+    // (a layer whose products do not run as the plane pair after all ignores o.below: the layer below keeps its pass.  dH in place of
+    //  the upstream gradient cannot be undone -- but whether THIS layer takes it depends on the batch description, the structure and
+    //  the switches alone, none of which the prediction of layer_hidden_sums_route saw differently)
+    if (o.dh_sums && !c.r.dh_given) {
+        set_error("eagcn_layer_backward: dH and its column sums were given, but the layer's route has no use for them");
+        return EAGCN_ERR_ARG;
+    }
     if (o.top_sums && c.r.bn2 != BN2_STAGED_FROM_READOUT) {
         set_error("eagcn_layer_backward: column sums from the read-out were given, but the layer's route has no use for them");
         return EAGCN_ERR_ARG;

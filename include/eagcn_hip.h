@@ -617,6 +617,16 @@ int eagcn_set_bx3_wide(int mode);
  * | 0: the reduction pass over the rows.  Returns the previous setting.
  * For tests and A/B runs; set it between steps (a forward and its backward must see the same value), before a graph is captured. */
 int eagcn_set_top_bn_sums(int on);
+/* The BatchNorm backward of a Concate layer BELOW a layer whose backward products run as the plane-GEMM pair (model engine, training,
+ * local BatchNorm, one stream, bond-list route): 1 (default; EAGCN_HIDDEN_BN_SUMS=0 in the environment presets 0): the launch of the dX
+ * product of the layer above (128 x 128 kernel) forms this layer's dH and the column sums of dH and dH xhat in a tail pass, no
+ * reduction launch over the rows
+ * | 0: the reduction pass.  Returns the previous setting.  For tests and A/B runs; set it between steps, before a graph is captured
+ * (a captured graph keeps its route). */
+int eagcn_set_hidden_bn_sums(int on);
+/* How many layer backward calls took that route since the last reset (a captured call counts when it is captured); reset != 0 clears
+ * the count.  For tests. */
+long eagcn_hidden_bn_sums_taken(int reset);
 /* ... of the TN problem (M, N, K) of eagcn_gemm_bx3_pair: its chunks are sized against the NT problem (M0, N0, K0) of the launch */
 int eagcn_bx3_pair_used_splits(int splits, int M, int N, int K, int M0, int N0, int K0);
 int eagcn_gemm_bx3(int tn, int M, int N, int K, const uint16_t* A, size_t a_pstride, int lda, int a_rows, const uint16_t* B,
