@@ -371,6 +371,10 @@ int launch_gemm(const GemmDesc& g0, hipStream_t s) {
     // contiguous runs are loaded as float4 when every run is 16-byte aligned and whole, else scalar
     g.vecA = (g.lda % 4) == 0 && ((g.ta ? g.M : g.K) % 4) == 0 && (reinterpret_cast<uintptr_t>(g.A) % 16) == 0;
     g.vecB = (g.ldb % 4) == 0 && ((g.tb ? g.K : g.N) % 4) == 0 && (reinterpret_cast<uintptr_t>(g.B) % 16) == 0;
+    // a reduction extent read on the device may end inside a float4 of a K-contiguous run (g.K is only the capacity): those
+    // operands take the scalar loads, which stop at the extent element by element
+    if (g.K_dev && g.ta == 0) g.vecA = 0;
+    if (g.K_dev && g.tb == 1) g.vecB = 0;
     if (g.splits > 1) EAGCN_CHECK_ARG(g.vecA && g.vecB, "gemm: split-K needs float4-aligned operands");
     // tile choice: EAGCN_GEMM_CFG=<id> forces one configuration (tools/gemm_bench.py)
     static const int forced = [] { const char* e = getenv("EAGCN_GEMM_CFG"); return e ? atoi(e) : -1; }();

@@ -14,6 +14,8 @@
 //   TN form  C[m,n] = sum_k A[k,m] B[k,n]  (dW = X^T.dP, K = packed rows):  lane (li, q) loads the float4
 //            A[k0 + 4q + s][m0 + 4 li .. +3] (16 lanes = one whole 256-byte tile row) and feeds FOUR 16-wide tiles (tile e
 //            holds the rows 4c + e: a permutation of the output rows / columns that the epilogue undoes with float4 stores).
+//   NN form  C[m,n] = sum_k A[m,k] B[k,n]  (eagcn_gemm_f32_sk only; no layer product takes it):  the A side of the NT form with
+//            the B side of the TN form, without the unclamped steady-state loop.
 // Scheduling: a launch is a fixed grid; the iteration space of up to two products (tiles x k-steps, counted on the device
 // from the actual extents) is cut into equal contiguous ranges, one per wave.  A tile cut between waves is finished by the
 // wave that owns its first k-step: the others park their accumulators in a workspace slot with write-through (sc1)
@@ -73,7 +75,10 @@ struct G3Sched {
 __device__ __forceinline__ f32x4 g3_sel(bool ok, f32x4 v) { return ok ? v : (f32x4){0.f, 0.f, 0.f, 0.f}; }
 
 // k-steps [kb, ke) of output tile `tile`.  mode 0: store, 1: park the partial + flag, 2: owner (add the contributors, store)
-template <bool TN, bool SCATTER>
+// NN (with TN = false; the stand-alone entry only): A as in the NT form, B stored [K][N] and loaded as in the TN form -- lane
+// (li, q) takes the float4 B[k0 + 4q + s][n0 + 4 li .. +3], whose component j is the operand of column-tile j at the k the
+// A side multiplies in step s; tiles, k order and epilogue are those of the NT form.
+template <bool TN, bool SCATTER, bool NN = false>
 __device__ __forceinline__ void g3_segment(const G2Prob& p, const DwScatter& sc, const int Mx, const int Kx, const int tile,
                                            const int kb, const int ke, const int mode, const int l, const int tile_end_global,
                                            const G3Sched& sched, float* __restrict__ ws, unsigned* __restrict__ flags,
@@ -92,7 +97,8 @@ __device__ __forceinline__ void g3_segment(const G2Prob& p, const DwScatter& sc,
         for (int i = 0; i < 4; ++i) {
             ap[i] = p.A + (size_t)max(min(m0 + 16 * i + li, Mx - 1), 0) * p.lda + 4 * q;
             // (tile j of the B side takes the rows 4 li + j, so that a lane's four results of a row are one float4)
-            bp[i] = p.B + (size_t)max(min(n0 + 4 * li + i, p.N - 1), 0) * p.ldb + 4 * q;
+            if constexpr (!NN) bp[i] = p.B + (size_t)max(min(n0 + 4 * li + i, p.N - 1), 0) * p.ldb + 4 * q;
+            else bp[i] = p.B + max(min(n0 + 4 * li, p.N - 4), 0);
         }
     } else {
         const float* a0 = p.A + max(min(m0 + 4 * li, p.M - 4), 0);
@@ -110,7 +116,8 @@ __device__ __forceinline__ void g3_segment(const G2Prob& p, const DwScatter& sc,
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 a[i] = *reinterpret_cast<const f32x4*>(ap[i] + kc);
-                b[i] = *reinterpret_cast<const f32x4*>(bp[i] + kc);
+                if constexpr (!NN) b[i] = *reinterpret_cast<const f32x4*>(bp[i] + kc);
+                else b[i] = *reinterpret_cast<const f32x4*>(bp[i] + (size_t)max(min(k0 + 4 * q + i, Kx - 1), 0) * p.ldb);
             }
         } else {
 #pragma unroll
@@ -137,7 +144,8 @@ __device__ __forceinline__ void g3_segment(const G2Prob& p, const DwScatter& sc,
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if constexpr (!TN) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][s], b[j][s], acc[i][j], 0, 0, 0);
+                    if constexpr (NN) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][s], b[s][j], acc[i][j], 0, 0, 0);
+                    else if constexpr (!TN) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][s], b[j][s], acc[i][j], 0, 0, 0);
                     else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s][i], b[s][j], acc[i][j], 0, 0, 0);
                 }
     };
@@ -147,7 +155,7 @@ __device__ __forceinline__ void g3_segment(const G2Prob& p, const DwScatter& sc,
         for (int u = 0; u < 4; ++u) {
             const bool v = TN ? (k0 + 4 * q + u < Kx) : (k0 + 4 * q < Kx);
             a[u] = g3_sel(v, a[u]);
-            b[u] = g3_sel(v, b[u]);
+            b[u] = g3_sel(NN ? (k0 + 4 * q + u < Kx) : v, b[u]);        // (NN: b[u] is the row k0 + 4q + u, as in the TN form)
         }
         mma_step(a, b);
     };
@@ -172,7 +180,7 @@ __device__ __forceinline__ void g3_segment(const G2Prob& p, const DwScatter& sc,
     // per step (TN: 16 rows further), and the eight loads of a step are spread over its 64 MFMAs by the scheduler directives
     // instead of forming a block of their own in front of them (the matrix pipe drained during every such block: the wave's
     // non-MFMA issue time was ~500 of ~2550 cycles per step).
-    if (it + 7 < ke) {
+    if (!NN && it + 7 < ke) {                        // (the stand-alone NN form runs on the clamped loads throughout)
         const float* fa[4];
         const float* fb[4];
         size_t stepA = 0, stepB = 0;
@@ -400,9 +408,9 @@ __device__ __forceinline__ int g3_logical(int b, int G) {
     return (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
 }
 
-// problem 0: NT or TN (TN0); optional problem 1 is always TN (the dW that rides with a dX), optionally scattered.
+// problem 0: NT, TN (TN0) or NN (NN0, alone); optional problem 1 is always TN (the dW that rides with a dX), optionally scattered.
 // XK (pairs only): XCD-local schedule (kernels.h g3_plan): dW leaves as one partial slab per segment at p1.C + x * xk_slab.
-template <bool TN0, bool HAS1, bool SCAT, bool XK>
+template <bool TN0, bool HAS1, bool SCAT, bool XK, bool NN0 = false>
 __global__ __launch_bounds__(256, G3_WAVES_PER_SIMD) void gemm3_kernel(G2Prob p0, G2Prob p1, DwScatter sc, float* __restrict__ ws,
                                                     unsigned* __restrict__ flags, int* __restrict__ err, size_t xk_slab) {
     const int G = gridDim.x;
@@ -477,7 +485,7 @@ __global__ __launch_bounds__(256, G3_WAVES_PER_SIMD) void gemm3_kernel(G2Prob p0
         const int seg_end = min(end, tile_end);
         const int ke = kb + (seg_end - it);
         const int mode = kb > 0 ? 1 : (seg_end < tile_end ? 2 : 0);
-        if (!second) g3_segment<TN0, SCAT && !HAS1>(p0, sc, M0, K0, tile, kb, ke, mode, l, tile_end, sched, ws, flags, err);
+        if (!second) g3_segment<TN0, SCAT && !HAS1, NN0>(p0, sc, M0, K0, tile, kb, ke, mode, l, tile_end, sched, ws, flags, err);
         else if constexpr (HAS1) g3_segment<true, SCAT>(p1, sc, M1, K1, tile, kb, ke, mode, l, tile_end, sched, ws, flags, err);
         it = seg_end;
     }
@@ -517,6 +525,13 @@ bool gemm3_ok(const GemmDesc& g) {
     if (g.ta == 1 && g.tb == 0) return (g.M & 3) == 0 && (g.N & 3) == 0 && !g.M_dev && g.M >= 4 && g.N >= 4 && (g.ldc & 3) == 0 &&
                                        g3_aligned(g.C);
     return false;
+}
+
+// NN: ta = 0, tb = 0 (eagcn_gemm_f32_sk only: the layer routes ask gemm3_ok and keep this form on the tiled kernel)
+static bool gemm3_nn_ok(const GemmDesc& g) {
+    if (g.ta != 0 || g.tb != 0 || g.M <= 0 || g.N < 4 || g.K < 4 || (g.N & 3) || (g.K & 3) || g.K_dev) return false;
+    if (!g3_aligned(g.A) || !g3_aligned(g.B) || (g.lda & 3) || (g.ldb & 3)) return false;
+    return (double)cdiv(g.M, G3_T) * cdiv(g.N, G3_T) * cdiv(g.K, G3_BK) < 1.0e9;
 }
 
 static G2Prob g3_prob(const GemmDesc& g) {
@@ -583,7 +598,7 @@ int gemm3_zero_job(void* workspace, size_t bytes, double* zero, int nzero, ZeroJ
 
 // one product; with `sc0` (TN only) the result goes to the per-view weight gradients instead of g.C
 int launch_gemm3(const GemmDesc& g, const DwScatter* sc0, void* workspace, size_t bytes, hipStream_t s) {
-    EAGCN_CHECK_ARG(gemm3_ok(g), "gemm: operands not 16-byte aligned / extents not multiples of 4 / unsupported form");
+    EAGCN_CHECK_ARG(gemm3_ok(g) || gemm3_nn_ok(g), "gemm: operands not 16-byte aligned / extents not multiples of 4 / unsupported form");
     EAGCN_CHECK_ARG(!sc0 || g.ta == 1, "gemm: the weight-gradient epilogue belongs to the TN form");
     float* ws; unsigned* flags;
     int rc = g3_prepare(workspace, bytes, &ws, &flags);
@@ -595,7 +610,9 @@ int launch_gemm3(const GemmDesc& g, const DwScatter* sc0, void* workspace, size_
     const G2Prob p = g3_prob(g);
     const int G = gemm3_grid();
     ProfScope ps(g.prof_tag, s, g.work > 0.0 ? g.work : 2.0 * g.M * g.N * g.K);
-    if (g.ta == 0) gemm3_kernel<false, false, false, false><<<G, 256, 0, s>>>(p, p, sc, ws, flags, g3_err_word(), 0);
+    if (g.ta == 0 && g.tb == 0)
+        gemm3_kernel<false, false, false, false, true><<<G, 256, 0, s>>>(p, p, sc, ws, flags, g3_err_word(), 0);
+    else if (g.ta == 0) gemm3_kernel<false, false, false, false><<<G, 256, 0, s>>>(p, p, sc, ws, flags, g3_err_word(), 0);
     else if (sc0) gemm3_kernel<true, false, true, false><<<G, 256, 0, s>>>(p, p, sc, ws, flags, g3_err_word(), 0);
     else gemm3_kernel<true, false, false, false><<<G, 256, 0, s>>>(p, p, sc, ws, flags, g3_err_word(), 0);
     EAGCN_LAUNCH_CHECK();

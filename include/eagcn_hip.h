@@ -642,7 +642,8 @@ int eagcn_gemm_bx3_pair(int M0, int N0, int K0, const uint16_t* A0, size_t a0_ps
 int eagcn_gemm_f32(int ta, int tb, int M, int N, int K, const float* A, int lda, const float* B,
                    int ldb, float* C, int ldc, void* stream);
 /* the same product with one extent read from device memory (M / K are then capacities): which = 0 the rows of A and C,
-   which = 2 the reduction length -- products over the packed rows of a capacity-sized batch index (eagcn_batch.meta[0]) */
+   which = 2 the reduction length -- products over the packed rows of a capacity-sized batch index (eagcn_batch.meta[0]);
+   any extent in any of the four forms: nothing of either operand at k >= extent enters the product, extent 0 gives zeros */
 int eagcn_gemm_f32_dev(int ta, int tb, int M, int N, int K, const float* A, int lda, const float* B,
                        int ldb, float* C, int ldc, const int32_t* extent_dev, int which, void* stream);
 

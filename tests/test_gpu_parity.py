@@ -380,6 +380,11 @@ def test_gemm_bf16x6_mode(ta, tb, M, N, K):
     e6 = ((c6 - ref).abs() / mag).max().item() / 2.0 ** -24
     e32 = ((c32 - ref).abs() / mag).max().item() / 2.0 ** -24
     assert e6 < max(2.0 * e32, 16.0), (e6, e32)                       # in units of fp32 epsilon of sum |a||b|
+    # the yardstick itself (bounds of tests/test_gpu_gemm_f32.py): a k-ordered fmaf chain stays within K roundings of the float64
+    # product, and within 4x of what torch.matmul (an independent fp32 implementation) reaches on the same operands, floor 8
+    e_torch = ((torch.matmul(A.float(), Bm.float()).double() - ref).abs() / mag).max().item() / 2.0 ** -24
+    print('fp32 MFMA path: e32 = %.3f, e_torch = %.3f (units of 2^-24 of sum |a||b|)' % (e32, e_torch))
+    assert e32 <= K and e32 <= max(8.0, 4.0 * e_torch), (e32, e_torch)
 
 
 def test_bad_inputs_raise():
