@@ -227,6 +227,9 @@ SIGNATURES = {
     'eagcn_stream_wait_timeouts': (C.c_int, []),
     'eagcn_stream_wait_reset': (None, []),
     'eagcn_adam_step': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int64, _fp, _fp, _fp, _fp]),
+    'eagcn_grad_norm_workspace_bytes': (C.c_size_t, []),
+    'eagcn_grad_norm': (C.c_int, [_fp, _fp, C.c_int64, _fp, C.c_int, _fp]),
+    'eagcn_adam_step_clipped': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     'eagcn_agg_wants_bond_lists': (C.c_int, [C.c_int, C.c_int]),
     'eagcn_agg_wants_bond_lists_for': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'eagcn_bx3_used_splits': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),

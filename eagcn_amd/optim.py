@@ -11,6 +11,14 @@ device memory, so the launch can be captured: ``EAGCN.fused_step(..., optimizer=
 update = one graph launch per training step).  Parameters that never receive a gradient (the reference leaves 48 of 177
 without one: unused AFM_BatchNorm affine terms, ``self_r`` / ``ave_A`` of the layer wrappers) are not touched, as with
 ``torch.optim.Adam``, which skips ``grad is None``.
+
+``max_grad_norm`` / ``skip_nonfinite`` (csrc/clip.hip) are ``torch.nn.utils.clip_grad_norm_`` in front of the step and a guard
+against NaN / Inf gradients, both on the device: one more launch measures the gradient's 2-norm (fp64, bit-reproducible) and counts
+its non-finite elements, the update launch scales the gradient by ``min(1, max_grad_norm / (norm + 1e-6))`` on its way in and, with
+``skip_nonfinite``, leaves parameters, moments and the step count alone when there was a NaN / Inf.  Two differences from torch:
+the gradient buffer is only READ (``p.grad`` keeps the unclipped values; ``clip_stats()['last_norm']`` is the norm that
+``clip_grad_norm_`` would have returned), and a skipped step protects parameters and moments but not the BatchNorm running
+statistics, which the forward updated before the gradient existed.
 """
 import ctypes as C
 
@@ -20,7 +28,7 @@ from . import _lib as L
 
 
 class FlatAdam:
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False):
         if getattr(model, 'structure', None) == 'GAT' or getattr(model, 'molfp_mode', None) == 'pool':
             raise L.EagcnHipError('FlatAdam covers the models with a model-level plan (Concate / Weighted_sum / GCN, sum / ave read-out); '
                                   'use torch.optim.Adam for GAT / pool models')
@@ -45,6 +53,27 @@ class FlatAdam:
         self.step_count = torch.zeros((), dtype=torch.int64, device=dev)
         self.ticket = torch.zeros((), dtype=torch.int32, device=dev)
         self._gather = None
+        # gradient clipping / non-finite skipping: with both at their defaults launch() is the single eagcn_adam_step; otherwise the
+        # norm launch and the clipped update.  Which of the two a captured step graph holds is fixed here, for the optimizer's life.
+        self.clipping = max_grad_norm is not None or bool(skip_nonfinite)
+        self.max_grad_norm = self._norm_value(max_grad_norm) if max_grad_norm is not None else None
+        self.skip_nonfinite = bool(skip_nonfinite)
+        if self.clipping:
+            lib = L.load()
+            self.norm_ws = torch.zeros(int(lib.eagcn_grad_norm_workspace_bytes()) // 8, dtype=torch.int64, device=dev)
+            self.clip = torch.tensor([float('inf') if self.max_grad_norm is None else self.max_grad_norm,
+                                      1.0 if self.skip_nonfinite else 0.0], dtype=torch.float64, device=dev)
+            self.stats = torch.zeros(4, dtype=torch.int64, device=dev)      # applied, skipped, clipped, last_norm (a double's bits)
+            # how many leading floats of every group of four are a live gradient: a parameter's elements, not the <= 3 pad words
+            # behind them (the weight-gradient epilogues store 16 bytes: a pad word of the gradient buffer holds anything) and not
+            # the slot of a frozen parameter
+            lanes = torch.zeros(n // 4, dtype=torch.uint8)
+            for p, o, k in zip(plan.params, plan.offsets, plan.sizes):
+                if p.requires_grad:
+                    lanes[o // 4:o // 4 + k // 4] = 4
+                    if k % 4:
+                        lanes[o // 4 + k // 4] = k % 4
+            self.lanes = lanes.to(dev)
         self.defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.param_groups = [dict(self.defaults, params=[p for p in plan.params if p.requires_grad])]
 
@@ -60,10 +89,39 @@ class FlatAdam:
         self.hyper[0] = float(lr)                  # (a device write: a captured step graph picks it up at its next replay)
         self.param_groups[0]['lr'] = float(lr)
 
+    @staticmethod
+    def _norm_value(x):
+        x = float(x)
+        if not x > 0.0:                            # (NaN included)
+            raise L.EagcnHipError('FlatAdam: max_grad_norm must be a positive number (float(\'inf\') measures without clipping), got %r' % (x,))
+        return x
+
+    def set_max_grad_norm(self, max_grad_norm):
+        """A device write, like set_lr: a captured step graph reads the new bound at its next replay."""
+        if not self.clipping:
+            raise L.EagcnHipError('FlatAdam was built without max_grad_norm / skip_nonfinite: its launch (and a step graph that captured '
+                                  'it) is the plain eagcn_adam_step; build the optimizer with max_grad_norm=... to clip')
+        if max_grad_norm is None:
+            raise L.EagcnHipError('FlatAdam: clipping cannot be switched off after construction (the launch sequence is captured); '
+                                  'set_max_grad_norm(float(\'inf\')) measures the norm and never clips')
+        self.max_grad_norm = self._norm_value(max_grad_norm)
+        self.clip[0] = self.max_grad_norm
+
+    def clip_stats(self):
+        """{'applied', 'skipped', 'clipped', 'last_norm'}: steps applied, steps skipped for a NaN / Inf gradient, applied steps whose
+        gradient was scaled down, and the 2-norm of the last step's gradient before clipping (what ``clip_grad_norm_`` returns; NaN /
+        Inf after such a gradient).  One device-to-host copy, which waits for the stream: the only synchronisation of the feature."""
+        if not self.clipping:
+            raise L.EagcnHipError('FlatAdam.clip_stats(): the optimizer was built without max_grad_norm / skip_nonfinite')
+        h = self.stats.cpu()
+        return {'applied': int(h[0]), 'skipped': int(h[1]), 'clipped': int(h[2]), 'last_norm': float(h[3:4].view(torch.float64)[0])}
+
     def reset_ticket(self):
         """After an aborted launch / failed capture: the kernel's last-workgroup ticket starts from zero again (it resets itself at the end
-        of every COMPLETED launch; left half counted, later launches would never advance the step count)."""
+        of every COMPLETED launch; left half counted, later launches would never advance the step count).  Likewise the norm launch's."""
         self.ticket.zero_()
+        if self.clipping:
+            self.norm_ws[2] = 0                    # (byte 16 of the workspace: the ticket and four reserved bytes)
 
     def _check_homes(self):
         """The module's parameters must still BE slices of the flat buffer (a later ``model.to()`` / ``.float()`` / assignment to
@@ -75,8 +133,22 @@ class FlatAdam:
                 raise L.EagcnHipError('FlatAdam: a parameter of the model no longer lives in the optimizer\'s flat buffer (the model was moved '
                                       'or a parameter\'s .data was re-assigned after the optimizer was built): build a new FlatAdam')
 
+    def _launch_norm(self, off, n, flat_grad, accumulate):
+        L.check(L.load().eagcn_grad_norm(C.c_void_p(flat_grad.data_ptr() + 4 * off), C.c_void_p(self.lanes.data_ptr() + off // 4), n,
+                                         C.c_void_p(self.norm_ws.data_ptr()), 1 if accumulate else 0,
+                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'eagcn_grad_norm')
+
     def _launch(self, off, n, flat_grad, advance):
         lib = L.load()
+        if self.clipping:
+            L.check(lib.eagcn_adam_step_clipped(C.c_void_p(self.flat.data_ptr() + 4 * off), C.c_void_p(flat_grad.data_ptr() + 4 * off),
+                                                C.c_void_p(self.exp_avg.data_ptr() + 4 * off), C.c_void_p(self.exp_avg_sq.data_ptr() + 4 * off),
+                                                n, C.c_void_p(self.hyper.data_ptr()), C.c_void_p(self.step_count.data_ptr()),
+                                                C.c_void_p(self.ticket.data_ptr()) if advance else C.c_void_p(0),
+                                                C.c_void_p(self.norm_ws.data_ptr()), C.c_void_p(self.clip.data_ptr()),
+                                                C.c_void_p(self.stats.data_ptr()),
+                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'eagcn_adam_step_clipped')
+            return
         L.check(lib.eagcn_adam_step(C.c_void_p(self.flat.data_ptr() + 4 * off), C.c_void_p(flat_grad.data_ptr() + 4 * off),
                                     C.c_void_p(self.exp_avg.data_ptr() + 4 * off), C.c_void_p(self.exp_avg_sq.data_ptr() + 4 * off), n,
                                     C.c_void_p(self.hyper.data_ptr()), C.c_void_p(self.step_count.data_ptr()),
@@ -85,8 +157,11 @@ class FlatAdam:
 
     def launch(self, flat_grad):
         """The update as one launch on the current stream (capturable): every slot of the flat buffer has a gradient (graph /
-        direct mode: the hot path produces all of them in every backward)."""
+        direct mode: the hot path produces all of them in every backward).  With clipping / skipping: the norm launch, then the
+        clipped update (two launches, both capturable)."""
         self._check_homes()
+        if self.clipping:
+            self._launch_norm(0, self.flat.numel(), flat_grad, False)
         self._launch(0, self.flat.numel(), flat_grad, True)
 
     @torch.no_grad()
@@ -112,12 +187,18 @@ class FlatAdam:
                 ranges[-1][1] = offs[i + 1]
             else:
                 ranges.append([offs[i], offs[i + 1]])
+        if self.clipping:                          # ONE norm over all live ranges (the first launch replaces the totals, the others add)
+            for j, (a, b) in enumerate(ranges):
+                self._launch_norm(a, b - a, self._gather, j > 0)
         for j, (a, b) in enumerate(ranges):
             self._launch(a, b - a, self._gather, j == len(ranges) - 1)
 
     def state_dict(self):
         g = self.param_groups[0]
-        return {'exp_avg': self.exp_avg.clone(), 'exp_avg_sq': self.exp_avg_sq.clone(), 'step': int(self.step_count),
+        counts = self.clip_stats() if self.clipping else {'applied': 0, 'skipped': 0, 'clipped': 0}
+        return {'max_grad_norm': self.max_grad_norm, 'skip_nonfinite': self.skip_nonfinite,
+                'applied': counts['applied'], 'skipped': counts['skipped'], 'clipped': counts['clipped'],
+                'exp_avg': self.exp_avg.clone(), 'exp_avg_sq': self.exp_avg_sq.clone(), 'step': int(self.step_count),
                 'hyper': self.hyper.clone(),
                 # the hyper-parameters as the Python floats they were given as (what load_state_dict restores from)
                 'param_group': {'lr': float(g['lr']), 'betas': tuple(float(b) for b in g['betas']), 'eps': float(g['eps']),
@@ -129,7 +210,19 @@ class FlatAdam:
         (0.99900001287...: exactly the 1.7e-5 error in 1 - beta2 the double hypers exist to avoid), so its entries are rounded
         back to the shortest decimal that has that image.
         One step count for the whole buffer: torch.optim.Adam keeps a count per PARAMETER; with the range-by-range update of the
-        autograd mode a parameter whose first gradient arrives in a later step gets the global count's bias correction here."""
+        autograd mode a parameter whose first gradient arrives in a later step gets the global count's bias correction here.
+        Clipping: a dict without the clipping keys, or one saved by an optimizer without clipping, leaves the constructor's
+        settings; one saved WITH clipping restores bound, skip flag and counters, and is refused by an optimizer built without."""
+        saved_on = sd.get('max_grad_norm') is not None or bool(sd.get('skip_nonfinite', False))
+        if saved_on and not self.clipping:
+            raise L.EagcnHipError('FlatAdam.load_state_dict: the state was saved with max_grad_norm / skip_nonfinite, this optimizer was '
+                                  'built without (clipping cannot be switched on after construction): build it with max_grad_norm=...')
+        if saved_on:
+            self.skip_nonfinite = bool(sd['skip_nonfinite'])
+            self.max_grad_norm = self._norm_value(sd['max_grad_norm']) if sd['max_grad_norm'] is not None else None
+            self.clip.copy_(torch.tensor([float('inf') if self.max_grad_norm is None else self.max_grad_norm,
+                                          1.0 if self.skip_nonfinite else 0.0], dtype=torch.float64))
+            self.stats[:3] = torch.tensor([int(sd.get(k, 0)) for k in ('applied', 'skipped', 'clipped')], dtype=torch.int64)
         self.exp_avg.copy_(sd['exp_avg'])
         self.exp_avg_sq.copy_(sd['exp_avg_sq'])
         self.step_count.fill_(int(sd['step']))

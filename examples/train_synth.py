@@ -5,6 +5,8 @@ HIP-graph replay of the step, periodic evaluation (per-task ROC-AUC / RMSE on de
     python examples/train_synth.py --dataset tox21 --steps 200 --batch 256
     python examples/train_synth.py --dataset tox21 --loader compact      # per-molecule data -> compact collate, every batch
                                                                         # padded to ITS maximum (utils.py:583), n_bucket=16
+    python examples/train_synth.py --dataset lipo --clip-norm 5 --skip-nonfinite   # clip_grad_norm_(5) in front of every update, and
+                                                                        # no update from a NaN / Inf gradient (both inside the step graph)
 """
 import argparse
 import os
@@ -41,6 +43,11 @@ def main():
     ap.add_argument('--optimizer', default='flat', choices=('flat', 'torch'),
                     help="train.py:303 Adam(lr, weight_decay): 'flat' = eagcn_amd.optim.FlatAdam (one kernel over a flat parameter "
                          "buffer, inside the captured step; models with a model-level plan), 'torch' = torch.optim.Adam")
+    ap.add_argument('--clip-norm', type=float, default=None,
+                    help='clip the gradient to this 2-norm before every update (torch.nn.utils.clip_grad_norm_): on the device with '
+                         "--optimizer flat (FlatAdam(max_grad_norm=...)), clip_grad_norm_ on the host's side of the step otherwise")
+    ap.add_argument('--skip-nonfinite', action='store_true',
+                    help='--optimizer flat: a step whose gradient holds a NaN / Inf changes no parameter and no moment')
     ap.add_argument('--loader', default='dense', choices=('dense', 'compact'),
                     help="dense: the reference's collate tensors; compact: bond list + unpadded rows (collate_compact)")
     args = ap.parse_args()
@@ -80,9 +87,19 @@ def main():
     model.apply(weights_init)
     if args.optimizer == 'flat' and not composed:
         from eagcn_amd.optim import FlatAdam
-        opt = FlatAdam(model, lr=lr, weight_decay=wd)          # built after .to(dev) and weights_init: it re-homes the parameters
+        # built after .to(dev) and weights_init: it re-homes the parameters
+        opt = FlatAdam(model, lr=lr, weight_decay=wd, max_grad_norm=args.clip_norm, skip_nonfinite=args.skip_nonfinite)
     else:
+        if args.skip_nonfinite:
+            sys.exit('--skip-nonfinite is FlatAdam\'s (--optimizer flat, not GAT / pool)')
         opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=wd)
+        if args.clip_norm is not None:                         # the reference script's one line, in front of every step()
+            plain_step = opt.step
+
+            def clipped_step(*a, **k):
+                torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.grad is not None], args.clip_norm)
+                return plain_step(*a, **k)
+            opt.step = clipped_step
     t0 = time.perf_counter()
     for step in range(args.steps):
         b, labels = train_set[step % len(train_set)]
@@ -98,6 +115,9 @@ def main():
             dt = time.perf_counter() - t0
             print('step %4d  loss %.5f  %s  (%.1f molecules/s incl. evaluation; %d captured runner(s))'
                   % (step, float(loss), shown, (step + 1) * args.batch / dt, len(model._runners)))
+    if getattr(opt, 'clipping', False):
+        # one device-to-host copy; a skipped step protects parameters and moments, not the BatchNorm running statistics
+        print('clip_stats: %r' % (opt.clip_stats(),))
 
 
 if __name__ == '__main__':

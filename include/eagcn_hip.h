@@ -554,6 +554,35 @@ int eagcn_mse_loss(const float* pred, const float* target, int n, float* loss, f
 int eagcn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const double* hyper_dev,
                     int64_t* step_dev, uint32_t* ticket_dev, void* stream);
 
+/* ---- gradient-norm clipping and non-finite step skipping for that step, on the device (csrc/clip.hip): what
+ * torch.nn.utils.clip_grad_norm_(params, max_norm) in front of optimizer.step() does, as two capturable launches, no host read.
+ *   eagcn_grad_norm: sum of squares (squares and sums in fp64) and count of non-finite values (NaN, +-Inf) over the LIVE elements of
+ *     grad[0..n) (n floats, a multiple of 4, 16-byte aligned).  live_lanes[i], i < n / 4, = how many LEADING floats of the i-th
+ *     group of four are live (0..4): a parameter's slot is its elements, then <= 3 pad words; a frozen parameter's slot is all 0.
+ *     live_lanes == NULL: every element is live.  At most 1024 workgroups of 256 each write one partial into their own slot; the
+ *     one that finishes last adds the slots in slot order: the totals are bit-identical from run to run (no floating-point atomics).
+ *     accumulate != 0: the totals are ADDED to the stored ones (several ranges of one step) instead of replacing them.
+ *   workspace: eagcn_grad_norm_workspace_bytes() = 32 + 1024 * 16 bytes, 16-byte aligned, ZERO before its first use (a launch
+ *     leaves the ticket 0):
+ *       byte  0  double   sumsq      total of the last launch (or of the accumulating launches since the last replacing one)
+ *       byte  8  uint64   n_bad      non-finite live elements, likewise
+ *       byte 16  uint32   ticket     workgroups finished in the running launch; 0 between launches
+ *       byte 20  12 bytes reserved
+ *       byte 32  1024 x { double sumsq ; uint64 n_bad }    one slot per workgroup
+ *   eagcn_adam_step_clipped: eagcn_adam_step with g' = coef * g in place of g (rounded to fp32 before the weight decay is added,
+ *     as torch scales p.grad before the step; grad itself is NOT written), coef = the fp32 image of
+ *     min(1, max_norm / (sqrt(sumsq) + 1e-6)) formed in double from norm_workspace's totals.  With coef == 1 every output bit equals
+ *     eagcn_adam_step's.  clip_dev = double[2] {max_norm (+Inf: measure, never clip), skip_nonfinite (0 / not 0)}.  When n_bad > 0
+ *     and skip_nonfinite is set NOTHING is written to param / exp_avg / exp_avg_sq and *step_dev does not advance.
+ *     The launch that brings ticket_dev (the last range of a step) also resets norm_workspace's ticket and updates
+ *       stats_dev: int64 applied | int64 skipped | int64 clipped (applied with coef < 1) | double last_norm (= sqrt(sumsq),
+ *       NaN / Inf when the gradient held one), 32 bytes, 8-byte aligned. */
+size_t eagcn_grad_norm_workspace_bytes(void);
+int eagcn_grad_norm(const float* grad, const uint8_t* live_lanes, int64_t n, void* workspace, int accumulate, void* stream);
+int eagcn_adam_step_clipped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const double* hyper_dev,
+                            int64_t* step_dev, uint32_t* ticket_dev, void* norm_workspace, const double* clip_dev,
+                            int64_t* stats_dev, void* stream);
+
 /* ---- evaluation outputs (train.py:130-211): append one batch to device-resident [cap][T] buffers at row `row_offset`:
  * scores = sigmoid(logits) (classification = 1) or the predictions (0), targets = labels, valid = label in {0,1} / 1 ---- */
 int eagcn_eval_append(const float* logits, const float* labels, int B, int T, int classification, float* scores,
