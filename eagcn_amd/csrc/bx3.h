@@ -79,7 +79,7 @@ __device__ __forceinline__ void bx_store1(const BxOut& o, int r, int c, float v)
 // Tail pass of an NT product that is the dX of a layer above a Concate layer (Y == nullptr: none).  The product's element (row, col)
 // is the upstream gradient of the layer BELOW at its packed column col.  The units store it as ever; behind its stream every compute
 // wave of the 128 x 128 kernel (gemm_bx3.hip; the 256 x 128 kernel does not carry the code and refuses such a problem) walks its
-// units again, reads its blocks back and stores that layer's dH = up m_row [sc Y' + sh > 0] keep / (1 - p) in their place -- formed
+// units again, reads its 64 x 64 blocks back (row-major, a lane takes four adjacent columns of sixteen rows: bx3_epi.h) and stores that layer's dH = up m_row [sc Y' + sh > 0] keep / (1 - p) in their place -- formed
 // exactly as layer.hip bn_bwd_reduce_kernel<false, false, DROP, false> forms it -- and writes sum dH and sum dH xhat per column as fp64
 // slabs [slab][fp][2], ONE slab per 64-row block of the product (slab m0 / 64: the waves of a tile own distinct (row block, column
 // block) pairs, nobody adds to anybody's sums).  Rows at or beyond the actual row count contribute nothing; ceil(rows / 64) slabs are

@@ -421,6 +421,9 @@ __device__ __forceinline__ BxStream bx_stream(const BxProb& p, int rot, int& rot
 }
 
 // up to two problems in one persistent launch (the dX / dW pair of a layer's backward): 4 compute waves + 2 loader waves per CU
+// (ONE workgroup per CU: the 144 KB of LDS allow no second one.  The tail pass (bx3_epi.h) is inlined and holds 176 registers behind
+//  barrier B_end, which takes bx3_kernel<1, 0> from 191 to 256 VGPRs -- free at one workgroup per CU; whoever makes room for two
+//  workgroups per CU has to move the pass out of line first)
 template <int NP, int DBG = 0>
 __global__ __launch_bounds__(64 * (BX_NC + BX_NL), 2) void bx3_kernel(BxProb p0, BxProb p1, int has1, int pair_policy) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);

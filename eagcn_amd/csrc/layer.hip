@@ -1586,6 +1586,9 @@ static int bwd_products(LayerBwd& c, const LayerOperands& o) {
         if (c.o.below && !c.bx_wide) {
             EAGCN_CHECK_ARG(c.o.below->Y && c.o.below->bn && c.o.below->row_m && c.o.below->slab && c.o.below->fp == bx.N && bx.ldc == bx.N,
                             "eagcn_layer_backward: incomplete description of the layer below");
+            // (bx3_epi.h: a lane takes four adjacent columns of dX and Y' at once -- inside or outside the matrix together)
+            EAGCN_CHECK_ARG((bx.N & 3) == 0 && (c.o.below->ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(c.o.below->slab) & 15) == 0,
+                            "eagcn_layer_backward: the tail pass of the dX product needs packed widths that are multiples of 4");
             bx.ep = *c.o.below;
             if (c.o.below_done) *c.o.below_done = true;
         }
