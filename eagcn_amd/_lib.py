@@ -323,6 +323,15 @@ SIGNATURES = {
     'eagcn_eval_metrics_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int]),
     'eagcn_eval_class_metrics': (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int, _fp, C.c_size_t, _fp, _fp]),
     'eagcn_eval_reg_metrics': (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int, _fp, C.c_size_t, _fp, _fp]),
+    'eagcn_rep_gather': (C.c_int, [C.POINTER(Batch), _fp, C.POINTER(Layout), _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp,
+                                   C.c_int64, _fp]),
+    'eagcn_rep_gather_dense': (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp,
+                                         C.c_int64, _fp]),
+    'eagcn_kmeans_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    'eagcn_kmeans_begin': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, C.c_int, _fp, C.c_double, _fp, C.c_size_t, _fp]),
+    'eagcn_kmeans_iterate': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, C.c_int, _fp, C.c_size_t, _fp]),
+    'eagcn_kmeans_finish': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, C.c_int, _fp, C.c_size_t, _fp]),
+    'eagcn_kmeans_assign': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp, _fp, C.c_size_t, _fp]),
     'eagcn_prof_enable': (None, [C.c_int]),
     'eagcn_prof_reset': (None, []),
     'eagcn_prof_ntags': (C.c_int, []),

@@ -1,0 +1,275 @@
+"""The evaluation-time consumers of the atom representations, on the device: the dump of train.py:213-287 (``dump_atom_rep``: the
+representations of the atoms whose sub-type lies in 1..18, with their sub-type and molecule index, plus the per-molecule graph
+representations / indices / labels / predictions) and the k-means clustering the reference's analysis runs over that dump on the host
+(kmeans_atomrep.py: ``kmeans_for_atom`` -> sklearn KMeans, compared with the atoms' sub-types through a confusion matrix).
+
+The reference copies the padded [B, N, F] matrix of every batch to the host, walks its B x N rows in a Python loop
+(train.py:264-268) and hands the result to scikit-learn.  Here the selected rows are gathered straight from the PACKED output of the
+last layer behind a device-side row counter (csrc/reps.hip: eagcn_rep_gather; the padded matrix is never formed, nothing is read by the
+host until ``finish``), and Lloyd's iterations run as HIP kernels that read every row once per iteration (eagcn_kmeans_*).
+
+One documented deviation from scikit-learn: a cluster that runs EMPTY keeps its centroid (``n_empty`` counts them); scikit-learn
+relocates it to the point farthest from its centre."""
+import ctypes as C
+from collections import namedtuple
+
+import torch
+
+from . import _lib as L
+
+RepDump = namedtuple('RepDump', 'X subtype mol_index graph_rep index labels outputs')
+KMeansResult = namedtuple('KMeansResult', 'centers labels inertia n_iter n_empty counts init_centers converged')
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+class RepBuffers:
+    """Device-resident dump of an evaluation pass: X [cap, F] fp32, subtype [cap] int32, mol_index [cap] int64 behind a device row
+    counter, grown geometrically on the host-known upper bound of the rows (every appended batch may select all its B x N atoms)."""
+
+    def __init__(self, device, subtype_range=(1, 18), cap=4096):
+        self.device = torch.device(device)
+        self.lo, self.hi = int(subtype_range[0]), int(subtype_range[1])
+        self.cap, self.bound, self.F = int(cap), 0, None
+        self.count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.X = self.sub = self.mol = None
+        self._mols = {'graph_rep': [], 'index': [], 'labels': [], 'outputs': []}
+
+    def _reserve(self, extra, F):
+        if self.F is None:
+            self.F = int(F)
+        elif self.F != int(F):
+            raise L.EagcnHipError('RepBuffers.append: representations of width %d after width %d' % (F, self.F))
+        need = self.bound + extra
+        if need >= 2 ** 31:
+            raise L.EagcnHipError('RepBuffers.append: %d rows do not fit the 32-bit row index' % need)
+        if self.X is not None and need <= self.cap:
+            return
+        old = None if self.X is None else (self.X[:self.bound], self.sub[:self.bound], self.mol[:self.bound])
+        self.cap = max(self.cap, need) if old is None else min(max(2 * self.cap, need), 2 ** 31 - 1)
+        self.X = torch.empty((self.cap, self.F), dtype=torch.float32, device=self.device)
+        self.sub = torch.empty(self.cap, dtype=torch.int32, device=self.device)
+        self.mol = torch.empty(self.cap, dtype=torch.int64, device=self.device)
+        if old is not None:
+            self.X[:self.bound], self.sub[:self.bound], self.mol[:self.bound] = old
+
+    def append(self, atom_rep, subtype, index, graph_rep=None, labels=None, outputs=None):
+        """One batch: `atom_rep` the model's LazyAtomRep (gathered from the packed rows) or a dense device [B, N, F] tensor,
+        `subtype` [B, N_in] integer sub-types, `index` [B] molecule indices.  No host synchronisation."""
+        lib = L.load()
+        subtype = torch.as_tensor(subtype).to(device=self.device, dtype=torch.int32).contiguous()
+        index = torch.as_tensor(index).to(device=self.device, dtype=torch.int64).contiguous().view(-1)
+        if subtype.dim() != 2 or subtype.shape[0] != index.numel():
+            raise L.EagcnHipError('RepBuffers.append: subtype %s and index %s do not describe one batch'
+                                  % (tuple(subtype.shape), tuple(index.shape)))
+        B, n_in = subtype.shape
+        args = getattr(atom_rep, '_args', None) if hasattr(atom_rep, '_ensure') else None
+        scratch = torch.empty(B * n_in, dtype=torch.int32, device=self.device)
+        if args is not None:
+            atom_rep._ensure()
+            idx = args[0]
+            packed, pad_row, layout = atom_rep.packed
+            c = idx.c
+            want = c.n_logical if c.n_logical > 0 else c.N
+            if (c.B, want) != (B, n_in):
+                raise L.EagcnHipError('RepBuffers.append: subtype is [%d, %d], the batch [%d, %d]' % (B, n_in, c.B, want))
+            self._reserve(B * n_in, layout.width)
+            L.check(lib.eagcn_rep_gather(idx.ref(), packed.data_ptr(), C.byref(layout.c), None if pad_row is None else pad_row.data_ptr(),
+                                         subtype.data_ptr(), self.lo, self.hi, index.data_ptr(), self.count.data_ptr(),
+                                         scratch.data_ptr(), self.X.data_ptr(), self.sub.data_ptr(), self.mol.data_ptr(), self.cap,
+                                         _stream()), 'eagcn_rep_gather')
+        else:
+            dense = atom_rep.cpu() if hasattr(atom_rep, '_ensure') else atom_rep          # (a LazyAtomRep that was already read)
+            dense = torch.as_tensor(dense).to(device=self.device, dtype=torch.float32).contiguous()
+            if dense.dim() != 3 or dense.shape[0] != B or dense.shape[1] < n_in:
+                raise L.EagcnHipError('RepBuffers.append: atom_rep %s does not match subtype [%d, %d]' % (tuple(dense.shape), B, n_in))
+            self._reserve(B * n_in, dense.shape[2])
+            L.check(lib.eagcn_rep_gather_dense(dense.data_ptr(), B, dense.shape[1], dense.shape[2], subtype.data_ptr(), n_in, self.lo,
+                                               self.hi, index.data_ptr(), self.count.data_ptr(), scratch.data_ptr(), self.X.data_ptr(),
+                                               self.sub.data_ptr(), self.mol.data_ptr(), self.cap, _stream()), 'eagcn_rep_gather_dense')
+        self.bound += B * n_in
+        for name, t in (('graph_rep', graph_rep), ('index', index), ('labels', labels), ('outputs', outputs)):
+            if t is not None:
+                self._mols[name].append(torch.as_tensor(t).detach().to(self.device).clone())
+
+    def finish(self):
+        """Reads the row count (the one host synchronisation).  RepDump of device tensors: X [n, F], subtype [n], mol_index [n] and
+        the per-molecule graph_rep / index / labels / outputs (None where nothing was appended)."""
+        n = int(self.count.item())
+        if self.X is None:
+            raise L.EagcnHipError('RepBuffers.finish: nothing has been appended')
+        per_mol = [torch.cat(v) if v else None for v in (self._mols[k] for k in ('graph_rep', 'index', 'labels', 'outputs'))]
+        return RepDump(self.X[:n], self.sub[:n], self.mol[:n], *per_mol)
+
+    def as_reference(self):
+        """The two host lists that train.py:272 and :280 save: [rows, sub-types, molecule indices] (one numpy entry per selected atom)
+        and [graph representations, molecule indices [M, 1], labels, predictions]."""
+        d = self.finish()
+        X, sub, mol = d.X.cpu().numpy(), d.subtype.cpu().numpy().astype('int64'), d.mol_index.cpu().numpy()
+        atoms = [[X[i] for i in range(len(X))], [sub[i] for i in range(len(sub))], [mol[i:i + 1] for i in range(len(mol))]]
+
+        def host(t, column=False):
+            if t is None:
+                return None
+            t = t.cpu().numpy()
+            return t.reshape(-1, 1) if column else t
+        return atoms, [host(d.graph_rep), host(d.index, True), host(d.labels), host(d.outputs)]
+
+
+@torch.no_grad()
+def dump_atom_rep(model, batches, subtype_range=(1, 18), buffers=None):
+    """train.py:213-287 on the device: eval-mode forward over `batches`, an iterable of (batch tuple, labels, subtype, index) -- a
+    batch tuple that starts with a CompactBonds is (bonds, afms, size), as in training.evaluate -- into a RepBuffers.  The model is
+    put back into the mode it was in."""
+    was_training = model.training
+    model.eval()
+    try:
+        for batch, labels, subtype, index in batches:
+            compact = hasattr(batch[0], 'bond_mol')
+            out, atom_rep, graph_rep = model.forward_compact(*batch) if compact else model(*batch)
+            if buffers is None:
+                buffers = RepBuffers(out.device, subtype_range)
+            buffers.append(atom_rep, subtype, index, graph_rep=graph_rep, labels=labels, outputs=out)
+    finally:
+        model.train(was_training)
+    return buffers
+
+
+# ---- k-means -----------------------------------------------------------------------------------------------------------------------
+
+def _a256(x):
+    return (int(x) + 255) & ~255
+
+
+def workspace_layout(n, F, k):
+    """Byte offsets of the caller-visible parts of a k-means workspace (include/eagcn_hip.h): state, centroids, counts, labels, mind."""
+    o_cen = 256
+    o_cnt = o_cen + _a256(4 * k * F)
+    o_lab = o_cnt + 256
+    o_mind = o_lab + _a256(4 * n)
+    return {'state': 0, 'centers': o_cen, 'counts': o_cnt, 'labels': o_lab, 'mind': o_mind, 'end': o_mind + _a256(4 * n)}
+
+
+def workspace_bytes(n, F, k):
+    """The header's formula for eagcn_kmeans_workspace_bytes, restated (tests compare the two)."""
+    G, F4, kk = min(-(-n // 64), 768), L.pad4(F), max(k, 2)
+    return workspace_layout(n, F, k)['end'] + _a256(8 * G * kk * F4) + _a256(64 * G) + _a256(4 * G) + _a256(8 * G) + 8192
+
+
+class _Problem:
+    """X as the kernels take it (fp32 device rows with unit column stride, ld >= F) and a workspace with typed views into it."""
+
+    def __init__(self, X, k):
+        if not isinstance(X, torch.Tensor) or not X.is_cuda or X.dtype != torch.float32 or X.dim() != 2:
+            raise L.EagcnHipError('kmeans: X must be a float32 [n, F] tensor on the MI355X (eagcn_amd has no CPU path)')
+        n, F = X.shape
+        if n > 1 and (X.stride(1) != 1 or X.stride(0) < F) or n == 1 and X.stride(1) != 1:
+            X = X.contiguous()
+        self.X, self.n, self.F, self.k = X, int(n), int(F), int(k)
+        self.ld = int(X.stride(0)) if n > 1 else int(F)
+        self.lib = L.load()
+        nbytes = self.lib.eagcn_kmeans_workspace_bytes(self.n, self.F, self.k)
+        self.ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=X.device)
+        o = workspace_layout(self.n, self.F, self.k)
+        self.state_i = self.ws[0:16].view(torch.int32)
+        self.state_d = self.ws[16:40].view(torch.float64)
+        self.centers = self.ws[o['centers']:o['centers'] + 4 * self.k * self.F].view(torch.float32).view(self.k, self.F)
+        self.counts = self.ws[o['counts']:o['counts'] + 4 * self.k].view(torch.int32)
+        self.labels = self.ws[o['labels']:o['labels'] + 4 * self.n].view(torch.int32)
+        self.mind = self.ws[o['mind']:o['mind'] + 4 * self.n].view(torch.float32)
+
+    def _common(self):
+        return (self.X.data_ptr(), self.n, self.F, self.ld, self.k)
+
+    def begin(self, init, tol):
+        L.check(self.lib.eagcn_kmeans_begin(*self._common(), init.data_ptr(), float(tol), self.ws.data_ptr(), self.ws.numel(), _stream()),
+                'eagcn_kmeans_begin')
+
+    def iterate(self):
+        L.check(self.lib.eagcn_kmeans_iterate(*self._common(), self.ws.data_ptr(), self.ws.numel(), _stream()), 'eagcn_kmeans_iterate')
+
+    def finish(self):
+        L.check(self.lib.eagcn_kmeans_finish(*self._common(), self.ws.data_ptr(), self.ws.numel(), _stream()), 'eagcn_kmeans_finish')
+
+    def assign(self, centers, labels, mind):
+        """labels / minimal squared distances of every row against `centers` [m, F], m <= k"""
+        L.check(self.lib.eagcn_kmeans_assign(self.X.data_ptr(), self.n, self.F, self.ld, centers.data_ptr(), centers.shape[0],
+                                             labels.data_ptr(), mind.data_ptr(), self.ws.data_ptr(), self.ws.numel(), _stream()),
+                'eagcn_kmeans_assign')
+
+
+def _draw(weights, generator):
+    """One index drawn with probability proportional to `weights` (a device vector), without a host read."""
+    w = torch.nan_to_num(weights.double(), nan=0.0, posinf=0.0).clamp_min_(0.0)
+    w = w + (w.sum() <= 0).to(w.dtype)                       # nothing left to choose by: uniform
+    if w.numel() <= 2 ** 24:
+        return torch.multinomial(w, 1, generator=generator)
+    cdf = torch.cumsum(w, 0)                                 # torch.multinomial stops at 2^24 categories
+    u = torch.rand(1, dtype=torch.float64, device=w.device, generator=generator) * cdf[-1]
+    return torch.searchsorted(cdf, u).clamp_(max=w.numel() - 1)
+
+
+def _init_centers(p, init, generator):
+    X, n, F, k = p.X, p.n, p.F, p.k
+    if isinstance(init, torch.Tensor):
+        if tuple(init.shape) != (k, F):
+            raise L.EagcnHipError('kmeans: init is %s, not [k, F] = [%d, %d]' % (tuple(init.shape), k, F))
+        return init.to(device=X.device, dtype=torch.float32).contiguous().clone()
+    if init == 'random':
+        rows = torch.randperm(n, device=X.device, generator=generator)[:k]
+        return X[rows, :F].contiguous()
+    if init != 'k-means++':
+        raise ValueError("kmeans: init must be a [k, F] tensor, 'random' or 'k-means++'")
+    # plain D^2 sampling, one candidate per step: the next centre is a row drawn with probability proportional to its squared
+    # distance to the nearest centre chosen so far (the assign pass's minimal distances)
+    centers = torch.empty((k, F), dtype=torch.float32, device=X.device)
+    centers[0] = X[_draw(torch.ones(n, device=X.device), generator), :F][0]
+    labels, mind = torch.empty_like(p.labels), torch.empty_like(p.mind)
+    for m in range(1, k):
+        p.assign(centers[:m], labels, mind)
+        centers[m] = X[_draw(mind, generator), :F][0]
+    return centers
+
+
+def kmeans(X, k, init='k-means++', n_init=1, max_iter=300, tol=1e-4, generator=None, sync_every=10):
+    """Lloyd's k-means over the rows of the device tensor X [n, F] (csrc/reps.hip; semantics in include/eagcn_hip.h: those of
+    sklearn.cluster.KMeans(algorithm='lloyd') except that an empty cluster keeps its centroid).  The host enqueues iterations in
+    groups of `sync_every` and reads the `done` word once per group; iterations behind convergence are no-ops on the device, so
+    the result does not depend on `sync_every`.  init: a [k, F] tensor, 'random' (k distinct rows) or 'k-means++' (drawn with
+    `generator`, a torch.Generator of X's device); n_init > 1 keeps the run of least inertia.  Returns a KMeansResult."""
+    k, n_init, max_iter, sync_every = int(k), int(n_init), int(max_iter), max(1, int(sync_every))
+    if n_init < 1 or max_iter < 1:
+        raise ValueError('kmeans: n_init and max_iter must be at least 1')
+    p = _Problem(X, k)
+    if isinstance(init, torch.Tensor):
+        n_init = 1
+    best = None
+    for _ in range(n_init):
+        c0 = _init_centers(p, init, generator)
+        p.begin(c0, tol)
+        it = 0
+        while it < max_iter:
+            m = min(sync_every, max_iter - it)
+            for _j in range(m):
+                p.iterate()
+            it += m
+            if int(p.state_i[0].item()):                     # the one host read of a group
+                break
+        p.finish()
+        done, n_iter, _changed, n_empty = p.state_i.tolist()
+        inertia = float(p.state_d[0].item())
+        if best is None or inertia < best.inertia:
+            best = KMeansResult(p.centers.clone(), p.labels.clone(), inertia, n_iter, n_empty, p.counts.clone().long(), c0, bool(done))
+    return best
+
+
+def confusion_matrix(y_true, labels, n_true, k):
+    """[n_true, k] int64 on the device: entry (t, c) counts the rows of true class t in cluster c (sklearn.metrics.confusion_matrix
+    with the classes 0 .. n_true - 1 against 0 .. k - 1)."""
+    y = torch.as_tensor(y_true).to(device=labels.device, dtype=torch.int64).view(-1)
+    c = labels.to(torch.int64).view(-1)
+    if y.numel() != c.numel():
+        raise ValueError('confusion_matrix: %d true classes for %d labels' % (y.numel(), c.numel()))
+    return torch.bincount(y * int(k) + c, minlength=int(n_true) * int(k)).view(int(n_true), int(k))

@@ -28,6 +28,9 @@
  *   eagcn_eval_append / eagcn_eval_class_metrics / eagcn_eval_reg_metrics
  *                        <- the evaluation functions train.py:130-211 (sklearn roc_curve + auc per task, RMSE; plus
  *                           average precision and MAE)
+ *   eagcn_rep_gather / eagcn_kmeans_*
+ *                        <- dump_atom_rep train.py:213-287 (the selected atoms' representations) and the Lloyd k-means the
+ *                           reference's analysis runs over them on the host (kmeans_atomrep.py)
  *   eagcn_model_forward / eagcn_model_backward
  *                        <- EAGCN.forward models.py:96-121 end to end (layers, read-out, Graph_BN,
  *                           den1/bn_den1/relu/dropout/den2/bn_den2/relu/den3) and its autograd backward
@@ -607,6 +610,54 @@ int eagcn_eval_class_metrics(const float* scores, const float* targets, const ui
                              size_t workspace_bytes, double* out, void* stream);
 int eagcn_eval_reg_metrics(const float* scores, const float* targets, const uint8_t* valid, int64_t rows, int T, void* workspace,
                            size_t workspace_bytes, double* out, void* stream);
+
+/* ---- atom-representation dump (train.py:213-287) on the device: the rows of the last layer's output whose sub-type lies in the closed
+ * range [lo, hi] (1 .. 18 in the reference, train.py:265), appended behind a DEVICE row counter.  Two launches, no host read.
+ *   packed / lay / pad_row: the last layer's packed output [T][ld], its layout and the row of the atoms that are not stored (NULL: zeros),
+ *     exactly the arguments of eagcn_unpack_rows; F = the layout's exact width.
+ *   subtype: int32 [B][N_in], N_in = b->n_logical if it is set, else b->N.  mol_index: int64 [B].
+ *   The selected atoms are written in ascending (molecule, atom) order -- the order of the reference's loop over the flattened batch:
+ *     X[*count ..][F] (exact columns, no segment padding), sub[*count ..], mol[*count ..]; then *count advances by their number.
+ *     A selected atom's row is bit for bit what eagcn_unpack_rows writes at [b][i], atoms beyond nat[b] included.
+ *   scratch: B * N_in int32 (contents irrelevant).  cap: rows of X / sub / mol; the caller guarantees *count + B * N_in <= cap < 2^31
+ *     (a row that would land at or beyond cap is dropped and *count stops at cap: no memory is overwritten).
+ *   eagcn_rep_gather_dense: the same from a dense [B][N][F] tensor, N >= N_in. */
+int eagcn_rep_gather(const eagcn_batch* b, const float* packed, const eagcn_layout* lay, const float* pad_row, const int32_t* subtype,
+                     int lo, int hi, const int64_t* mol_index, int64_t* count, int32_t* scratch, float* X, int32_t* sub, int64_t* mol,
+                     int64_t cap, void* stream);
+int eagcn_rep_gather_dense(const float* dense, int B, int N, int F, const int32_t* subtype, int N_in, int lo, int hi,
+                           const int64_t* mol_index, int64_t* count, int32_t* scratch, float* X, int32_t* sub, int64_t* mol, int64_t cap,
+                           void* stream);
+
+/* ---- k-means (Lloyd) over device rows X[n][ld] (fp32, F <= ld columns used; rows need not be 16-byte aligned), on the caller's stream,
+ * no host read, no floating-point atomics: results are bit-identical from run to run.  In fp64 terms
+ *     tol_abs = tol * mean_f var_n(X[:, f])                                   (scikit-learn's scaling; eagcn_kmeans_begin)
+ *     one iteration: l = argmin_c sum_f (x_f - c_f)^2 (direct differences, lowest index on ties); Cn[c] = mean of the rows with l == c,
+ *       or C[c] where there is none (an EMPTY CLUSTER KEEPS ITS CENTROID; scikit-learn relocates it); shift = sum (Cn - C)^2; C = Cn;
+ *       n_iter += 1; done when no label changed against the iteration before, or shift <= tol_abs     (eagcn_kmeans_iterate)
+ *     labels = argmin against the final C, inertia = the sum of the minimal distances, counts per cluster     (eagcn_kmeans_finish)
+ *   eagcn_kmeans_iterate enqueues ONE iteration (three launches); every launch returns at once when `done` is set, so iterations
+ *   enqueued behind convergence change nothing and the host may read `done` as rarely as it likes.  Distances are fp32 sums in a fixed
+ *   order, cluster sums fp64 (per workgroup in LDS, then over the workgroups' slabs in slab order), centroids stored in fp32.
+ *   Envelope: 1 <= k <= 16, 1 <= F <= 1024, k * pad4(F) <= 8192, k <= n < 2^31, ld >= F; anything else is refused before any HIP call.
+ *   workspace: 256-byte aligned, at least eagcn_kmeans_workspace_bytes(n, F, k) bytes, written by eagcn_kmeans_begin.  With
+ *   a(x) = x rounded up to a multiple of 256, F4 = pad4(F), G = min(ceil(n / 64), 768) and kk = max(k, 2) it is, in this order,
+ *       256            state: int32 done | n_iter | changed | n_empty, then double inertia | shift | tol_abs (bytes 0 .. 39)
+ *       a(4 k F)       centroids [k][F] fp32
+ *       256            counts [k] int32 (of the last iteration; of the final labels after eagcn_kmeans_finish)
+ *       a(4 n)         labels [n] int32
+ *       a(4 n)         minimal squared distances [n] fp32 (of the last assignment pass)
+ *       a(8 G kk F4) + a(64 G) + a(4 G) + a(8 G) + 8192      per-workgroup sums / counts / changed labels / inertia, block partials
+ *   (0 for arguments outside the envelope).
+ *   eagcn_kmeans_assign: the assignment pass alone against any centres [k][F]: labels [n] and minimal squared distances [n] (the
+ *   D^2 weights of a k-means++ seeding); the workspace (sized for this k or a larger one) is scratch. */
+size_t eagcn_kmeans_workspace_bytes(int64_t n, int F, int k);
+int eagcn_kmeans_begin(const float* X, int64_t n, int F, int ld, int k, const float* init, double tol, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int eagcn_kmeans_iterate(const float* X, int64_t n, int F, int ld, int k, void* workspace, size_t workspace_bytes, void* stream);
+int eagcn_kmeans_finish(const float* X, int64_t n, int F, int ld, int k, void* workspace, size_t workspace_bytes, void* stream);
+int eagcn_kmeans_assign(const float* X, int64_t n, int F, int ld, const float* centers, int k, int32_t* labels, float* mind,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* Matrix-core path of the layer products (the reference's torch.mm and its two autograd products, layers.py:40):
  *   0 = fp32 MFMA: exact fp32 products, a k-ordered fmaf chain (csrc/gemm3.hip);
