@@ -614,7 +614,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 template <bool TRANS>
 static int launch_agg_t(const AggArgs& a, int ct, dim3 grid, bool ksplit, hipStream_t s) {
     switch (ct) {
-    static const int nw2 = [] { const char* e = getenv("EAGCN_AGG_NW"); return e ? atoi(e) : 4; }();
+    static const int nw2 = env_int("EAGCN_AGG_NW", 4);
 #define EAGCN_AGG_CASE(N) case N: if (ksplit && nw2 == 2) agg2_kernel<N, TRANS><<<grid, 128, 0, s>>>(a); \
                                   else if (ksplit) agg_kernel<N, TRANS><<<grid, 256, 0, s>>>(a); \
                                   else agg_wave_kernel<N, TRANS><<<grid, 256, 0, s>>>(a); break;
@@ -632,12 +632,12 @@ static int launch_agg_t(const AggArgs& a, int ct, dim3 grid, bool ksplit, hipStr
 // the allocator give up; an 8-tile layer runs the 9-tile instantiation with its last tile masked off instead);
 // EAGCN_AGG_MAXCT changes the cap (1..10)
 static int agg_max_ct() {
-    static const int v = [] { const char* e = getenv("EAGCN_AGG_MAXCT"); const int x = e ? atoi(e) : 9; return x < 1 ? 1 : (x > 10 ? 10 : x); }();
+    static const int v = std::max(1, std::min(env_int("EAGCN_AGG_MAXCT", 9), 10));
     return v;
 }
 // wave-per-tile variant: XCD-contiguous tile handout (agg_wave_body); EAGCN_AGG_XCD=0 hands the tiles out in dispatch order
 static int agg_xcd() {
-    static const int v = [] { const char* e = getenv("EAGCN_AGG_XCD"); return e ? atoi(e) : 1; }();
+    static const int v = env_int("EAGCN_AGG_XCD", 1);
     return v;
 }
 static int agg_pick_ct(int tmax, int nchunk) {
@@ -651,7 +651,7 @@ static int agg_pick_ct(int tmax, int nchunk) {
 // wave-per-tile kernel): equal at B = 256 (0.455 ms either way), wave-per-tile ahead at B = 512 (Tox21 0.641 -> 0.616 ms,
 // Lipo 3-layer 1.557 -> 1.439 ms): the switch is at 256 (EAGCN_AGG_KSPLIT_MAXB).
 bool agg_ksplit(const eagcn_batch* b) {
-    static const int maxb = [] { const char* e = getenv("EAGCN_AGG_KSPLIT_MAXB"); return e ? atoi(e) : 256; }();
+    static const int maxb = env_int("EAGCN_AGG_KSPLIT_MAXB", 256);
     return b->B <= maxb;
 }
 // number of workgroups along x = number of BatchNorm stat slabs
@@ -833,8 +833,6 @@ __device__ __forceinline__ void edge_grad_body(const EdgeArgs& a, const int bx, 
     }
 }
 
-__global__ __launch_bounds__(256) void edge_grad_kernel(EdgeArgs a) { edge_grad_body(a, blockIdx.x, blockIdx.y, gridDim.x); }
-
 // Transposed aggregation and edge gradients of one layer in ONE grid: both only read dY' (and saved
 // activations), both are chains of dependent loads that leave most of a CU idle, and neither fills the chip
 // alone -- side by side they overlap instead of running back to back.  Workgroups [0, agg_gx) of every grid row
@@ -852,17 +850,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CT >= 7 &&
 
 // one workgroup per 16 packed rows; workgroups beyond the actual row count exit at once
 int edge_grid_x(const eagcn_batch* b) { return std::max(1, std::min(cdiv(b->T, 16), 1024)); }
-
-int launch_edge_grad(const EdgeArgs& a_in, hipStream_t s) {
-    EdgeArgs a = a_in;
-    a.xcd = (agg_xcd() && !agg_ksplit(&a.bt)) ? 1 : 0;
-    if (a.bt.T == 0) return EAGCN_OK;
-    dim3 grid(edge_grid_x(&a.bt), a.vc.K);
-    ProfScope ps(PROF_EDGE, s);
-    edge_grad_kernel<<<grid, 256, 0, s>>>(a);
-    EAGCN_LAUNCH_CHECK();
-    return EAGCN_OK;
-}
 
 // transposed aggregation + edge gradients in one launch (see agg_edge_kernel)
 int launch_agg_edge(AggArgs a, const EdgeArgs& e_in, hipStream_t s) {

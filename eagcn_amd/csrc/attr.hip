@@ -117,8 +117,10 @@ extern "C" size_t eagcn_attr_acc_elems(const eagcn_batch* b, const eagcn_model* 
 extern "C" int eagcn_attr_pack_input(const eagcn_batch* b, const eagcn_model* m, const float* afm, const float* baseline, float alpha,
                                      void* saved, size_t saved_bytes, void* stream) {
     EAGCN_CHECK_ARG(b && m && afm && saved, "eagcn_attr_pack_input: null argument");
+    int rc = check_reserved_null(m->aux_stream, "eagcn_attr_pack_input", "eagcn_model.aux_stream");
+    if (rc) return rc;
     float* x0 = nullptr;
-    int rc = model_input_slot(b, m, saved, saved_bytes, &x0, "eagcn_attr_pack_input");
+    rc = model_input_slot(b, m, saved, saved_bytes, &x0, "eagcn_attr_pack_input");
     if (rc) return rc;
     if (b->T == 0) return EAGCN_OK;
     const eagcn_layout* in = &m->layer[0].in;
@@ -154,5 +156,7 @@ extern "C" int eagcn_attr_finalize(const eagcn_batch* b, const eagcn_model* m, c
                                    float* attr, float* score, void* stream) {
     EAGCN_CHECK_ARG(b && m && afm && attr && score, "eagcn_attr_finalize: null argument");
     EAGCN_CHECK_ARG(b->T == 0 || acc, "eagcn_attr_finalize: null accumulator");
+    const int rc = check_reserved_null(m->aux_stream, "eagcn_attr_finalize", "eagcn_model.aux_stream");
+    if (rc) return rc;
     return launch_attr_dense(b, &m->layer[0].in, acc, afm, baseline, attr, score, (hipStream_t)stream);
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/eagcn_hip.h"
@@ -249,16 +250,10 @@ struct ProfScope {
     ~ProfScope() { if (on) prof_end(tag, s); }
 };
 
-// ---- fork / join between the main stream and an auxiliary stream (events from a small pool; the
-// record/wait pairs are legal inside stream capture and become graph dependencies) ---------------
-hipEvent_t pool_event();
-inline int stream_after(hipStream_t waiter, hipStream_t producer) {
-    hipEvent_t e = pool_event();
-    if (!e) return EAGCN_ERR_HIP;
-    if (hipEventRecord(e, producer) != hipSuccess) return EAGCN_ERR_HIP;
-    if (hipStreamWaitEvent(waiter, e, 0) != hipSuccess) return EAGCN_ERR_HIP;
-    return EAGCN_OK;
-}
+// ---- switches and tunables from the environment (a caller keeps the value in a `static const`: each is read once) ----
+inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+// a 0 / 1 switch: a default-on switch goes off with "0", a default-off switch on with "1"; anything else leaves the default
+inline bool env_flag(const char* name, bool dflt) { const char* v = getenv(name); return v ? (dflt ? v[0] != '0' : v[0] == '1') : dflt; }
 
 // ---- internal launchers (defined across the .hip files) -----------------------------------------
 struct GemmDesc {

@@ -339,7 +339,7 @@ static int launch_cfg(const GemmDesc& g, hipStream_t s) {
 // "bf16" of BASELINE.json configs[1]; NOT the parity path (products carry 2^-9 relative rounding per operand).
 // default 3: operand planes written by the producers, products on the bf16 matrix cores (gemm_bx3.hip) -- the whole GPU parity
 // suite is green in this mode with the tolerances of the fp32 MFMA path (profiles/r04_parity_report.txt)
-static int g_gemm_x6 = [] { const char* e = getenv("EAGCN_GEMM_X6"); return e ? atoi(e) : 3; }();
+static int g_gemm_x6 = env_int("EAGCN_GEMM_X6", 3);
 // (modes 3 / 4 -- operand planes written by the producers, gemm_bx3.hip -- are decided per layer in layer.hip; whatever still
 //  reaches this file in those modes runs on the fp32 matrix path)
 static int use_x6(const GemmDesc& g) { return ((g_gemm_x6 == 1 || g_gemm_x6 == 2) && g.K >= 64 && g.prof_tag != PROF_HEAD) ? g_gemm_x6 : 0; }
@@ -358,7 +358,7 @@ static int launch_x6_cfg(const GemmDesc& g, hipStream_t s) {
 static int launch_x6(const GemmDesc& g, hipStream_t s, int mode) {
     if (mode == 2) return launch_x6_cfg<64, 64, 2>(g, s);
     // EAGCN_X6_TILE = 0: 64x64, 1: 128x64, 2: 128x128 (tools/gemm_bench.py)
-    static const int tile = [] { const char* e = getenv("EAGCN_X6_TILE"); return e ? atoi(e) : 0; }();
+    static const int tile = env_int("EAGCN_X6_TILE", 0);
     if (tile == 2 && g.M > 64 && g.N > 64) return launch_x6_cfg<128, 128, 1>(g, s);
     if (tile >= 1 && g.M > 64) return launch_x6_cfg<128, 64, 1>(g, s);
     return launch_x6_cfg<64, 64, 1>(g, s);
@@ -377,7 +377,7 @@ int launch_gemm(const GemmDesc& g0, hipStream_t s) {
     if (g.K_dev && g.tb == 1) g.vecB = 0;
     if (g.splits > 1) EAGCN_CHECK_ARG(g.vecA && g.vecB, "gemm: split-K needs float4-aligned operands");
     // tile choice: EAGCN_GEMM_CFG=<id> forces one configuration (tools/gemm_bench.py)
-    static const int forced = [] { const char* e = getenv("EAGCN_GEMM_CFG"); return e ? atoi(e) : -1; }();
+    static const int forced = env_int("EAGCN_GEMM_CFG", -1);
     int cfg = forced;
     if (cfg < 0 && use_x6(g)) return launch_x6(g, s, use_x6(g));
     if (cfg < 0) {

@@ -492,10 +492,6 @@ __global__ __launch_bounds__(256, G3_WAVES_PER_SIMD) void gemm3_kernel(G2Prob p0
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-static int g3_env(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
 int gemm3_grid() {           // workgroups of four autonomous waves: one wave per SIMD (two measured 40 % slower: the fragment
                              // streams of eight waves no longer fit the CU's 32 KB vector cache)
     // default: one workgroup per CU of THIS device (the hand-off needs the whole grid co-resident; 256 on an MI355X)
@@ -505,7 +501,7 @@ int gemm3_grid() {           // workgroups of four autonomous waves: one wave pe
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
             cus = prop.multiProcessorCount;
         (void)hipGetLastError();               // (no device in the build container: keep the nominal 256)
-        int v = g3_env("EAGCN_GEMM3_WGS", cus);
+        int v = env_int("EAGCN_GEMM3_WGS", cus);
         return std::max(8, std::min(v, G3_MAX_RANGES / 4));
     }();
     return g;
@@ -623,7 +619,7 @@ int launch_gemm3(const GemmDesc& g, const DwScatter* sc0, void* workspace, size_
 bool gemm3_xk_enabled() {
     // measured on MI355X (gpurun_out/r3a): 8x less fabric traffic and NOT faster (pair 77 vs 71 us stand-alone at 4809
     // rows, 259 vs 233 us at 19200) -- the kernel is not bound by operand fetch; off unless EAGCN_GEMM3_XK=1
-    static const bool on = g3_env("EAGCN_GEMM3_XK", 0) != 0;
+    static const bool on = env_int("EAGCN_GEMM3_XK", 0) != 0;
     return on;
 }
 

@@ -120,7 +120,7 @@ __device__ __forceinline__ int bx_total_tiles(const BxProb& p, const BxStream& s
 // Two waves do nothing but LDS-DMA: wave lw requests every second 1 KB piece of the three (NP) planes of both operands of a
 // k-tile -- 8 NP instructions -- for k-tile k + 2 while the compute waves multiply k-tile k.  (Issued by the compute waves
 // themselves the twelve requests per wave and k-tile held the wave's issue port while the matrix pipe idled: fill alone 65 us,
-// products alone 59 us, together 99 us at 19 200 x 400 x 720 -- DESIGN.md section 4 (probes EAGCN_BX3_DBG=1 / 2).)
+// products alone 59 us, together 99 us at 19 200 x 400 x 720 -- DESIGN.md section 4.)
 template <bool TN, int NP>
 __device__ __forceinline__ void bx_loader(const BxProb& p, const BxStream& st, const int lw) {
     constexpr int PPL = NP * (BX_APW + BX_BPW);
@@ -218,7 +218,7 @@ __device__ __forceinline__ void bx_loader(const BxProb& p, const BxStream& st, c
 //   TN: 16-lane block b = lane >> 4, c = lane & 15: the block reads [4 k][16 rows]; the lane supplies the address of k-row
 //       (c >> 2), rows 4 (c & 3) .. + 3 of the block and receives the 4 k of row c: blocks 0 / 1 = rows 0-15 / 16-31 at
 //       k 0-7, blocks 2 / 3 the same rows at k 8-15 (operand layout of the 32 x 32 x 16 MFMA)
-template <bool TN, int NP, int DBG>
+template <bool TN, int NP>
 __device__ __forceinline__ void bx_compute(const BxProb& p, const int pidx, const BxStream& st_, const int wave) {
     // the stream in SCALAR registers (it is uniform over the wave, but not provably: a TN stream's chunk count goes through a wave-wide
     // minimum): with the second walk behind the k-loop it is live across the loop, in vector registers the loop does not have
@@ -281,7 +281,6 @@ __device__ __forceinline__ void bx_compute(const BxProb& p, const int pidx, cons
     };
     bx_bf16x8 a0[2][NP], b0[2][NP], a1[2][NP], b1[2][NP];
     auto load_set = [&](bx_bf16x8 (&fa_)[2][NP], bx_bf16x8 (&fb_)[2][NP], int stg, int s) __attribute__((always_inline)) {
-        if constexpr (DBG == 1) return;
         const unsigned char* sa = bx_smem + stg * BX_STAGE;
         const unsigned char* sbp = sa + 3 * BX_APL;
 #pragma unroll
@@ -297,7 +296,6 @@ __device__ __forceinline__ void bx_compute(const BxProb& p, const int pidx, cons
 #define EAGCN_BX_PROD(ACC, PA, PB)                                                                                     \
     _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int jj = 0; jj < 2; ++jj)                     \
         ACC[i][jj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][PA], bf[jj][PB], ACC[i][jj], 0, 0, 0);
-        if constexpr (DBG == 1) return;                // (probe: fill only)
         if constexpr (NP == 3) {
             EAGCN_BX_PROD(lo, 2, 0)
             EAGCN_BX_PROD(lo, 1, 1)
@@ -422,9 +420,9 @@ __device__ __forceinline__ BxStream bx_stream(const BxProb& p, int rot, int& rot
 
 // up to two problems in one persistent launch (the dX / dW pair of a layer's backward): 4 compute waves + 2 loader waves per CU
 // (ONE workgroup per CU: the 144 KB of LDS allow no second one.  The tail pass (bx3_epi.h) is inlined and holds 176 registers behind
-//  barrier B_end, which takes bx3_kernel<1, 0> from 191 to 256 VGPRs -- free at one workgroup per CU; whoever makes room for two
+//  barrier B_end, which takes bx3_kernel<1> from 191 to 256 VGPRs -- free at one workgroup per CU; whoever makes room for two
 //  workgroups per CU has to move the pass out of line first)
-template <int NP, int DBG = 0>
+template <int NP>
 __global__ __launch_bounds__(64 * (BX_NC + BX_NL), 2) void bx3_kernel(BxProb p0, BxProb p1, int has1, int pair_policy) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int rot = 0, rot1 = 0;
@@ -440,19 +438,14 @@ __global__ __launch_bounds__(64 * (BX_NC + BX_NL), 2) void bx3_kernel(BxProb p0,
         const BxStream st = bx_stream(p, rot, rot1, ou, okt);
         rot = rot1;
         if (wave < BX_NC) {
-            if (p.tn) bx_compute<true, NP, DBG>(p, pidx, st, wave); else bx_compute<false, NP, DBG>(p, pidx, st, wave);
+            if (p.tn) bx_compute<true, NP>(p, pidx, st, wave); else bx_compute<false, NP>(p, pidx, st, wave);
         } else {
-            if constexpr (DBG != 2) {
-                if (p.tn) bx_loader<true, NP>(p, st, wave - BX_NC); else bx_loader<false, NP>(p, st, wave - BX_NC);
-            } else {                                   // (probe: products only, on whatever the LDS holds)
-                const int total = bx_total_tiles(p, st);
-                for (int k = 0; k < total + 2; ++k) __builtin_amdgcn_s_barrier();
-            }
+            if (p.tn) bx_loader<true, NP>(p, st, wave - BX_NC); else bx_loader<false, NP>(p, st, wave - BX_NC);
         }
     }
 }
 // bx3_epi.h reads problem `pidx` as element pidx of the kernel's argument segment: the two problems are the FIRST two parameters
-static_assert(std::is_same<decltype(&bx3_kernel<3, 0>), void (*)(BxProb, BxProb, int, int)>::value, "bx3_epi.h: the kernel's arguments start with its two BxProb's");
+static_assert(std::is_same<decltype(&bx3_kernel<3>), void (*)(BxProb, BxProb, int, int)>::value, "bx3_epi.h: the kernel's arguments start with its two BxProb's");
 
 // ---- operand producers -----------------------------------------------------------------------------------------------------------
 // fp32 matrix [rows][ld] -> three bf16 planes (stand-alone conversion: C-ABI entry, tests, layer-level path; the model engine's
@@ -470,7 +463,7 @@ __global__ __launch_bounds__(256) void bx3_split_kernel(const float* __restrict_
 }
 
 bool bx3_pair_policy() {
-    static const bool v = [] { const char* e = getenv("EAGCN_BX3_PAIR_POLICY"); return !(e && e[0] == '0'); }();
+    static const bool v = env_flag("EAGCN_BX3_PAIR_POLICY", true);
     return v;
 }
 
@@ -481,18 +474,16 @@ int bx3_grid() {
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
             cus = prop.multiProcessorCount;
         (void)hipGetLastError();
-        const char* e = getenv("EAGCN_BX3_WGS");
-        int v = e ? atoi(e) : cus;
-        return std::max(8, v / 8 * 8);
+        return std::max(8, env_int("EAGCN_BX3_WGS", cus) / 8 * 8);
     }();
     return g;
 }
 
 // ---- which of the two kernels (bx3.h) -------------------------------------------------------------------------------------------------
-static int g_bx3_wide = [] { const char* e = getenv("EAGCN_BX3_WIDE"); return e ? atoi(e) : -1; }();      // -1 auto | 0 never | 1 always
+static int g_bx3_wide = env_int("EAGCN_BX3_WIDE", -1);      // -1 auto | 0 never | 1 always
 static int bx3_wide_min(bool pair) {
-    static const int v1 = [] { const char* e = getenv("EAGCN_BX3_WIDE_MIN"); return e ? atoi(e) : 80; }();
-    static const int v2 = [] { const char* e = getenv("EAGCN_BX3_WIDE_MIN_PAIR"); return e ? atoi(e) : 50; }();
+    static const int v1 = env_int("EAGCN_BX3_WIDE_MIN", 80);
+    static const int v2 = env_int("EAGCN_BX3_WIDE_MIN_PAIR", 50);
     return pair ? v2 : v1;
 }
 int bx3_pick_wide(const BxProb& p0, const BxProb* p1, int rows_hint) {
@@ -538,15 +529,15 @@ bool bx3_ok(const BxProb& p) {
     return !p.M_dev && p.M <= p.A.ld && p.N <= p.B.ld && p.splits >= 1 && (p.splits == 1 || p.slab >= (size_t)p.M * p.ldc);
 }
 
-template <int NP, int DBG = 0>
+template <int NP>
 static int bx3_launch_cfg(const BxProb& p0, const BxProb* p1, hipStream_t s) {
     constexpr int lds = BX_NS * BX_STAGE;
     static bool attr_done = false;
     if (!attr_done) {
-        EAGCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bx3_kernel<NP, DBG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        EAGCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bx3_kernel<NP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         attr_done = true;
     }
-    bx3_kernel<NP, DBG><<<bx3_grid(), 64 * (BX_NC + BX_NL), lds, s>>>(p0, p1 ? *p1 : p0, p1 ? 1 : 0, bx3_pair_policy() ? 1 : 0);
+    bx3_kernel<NP><<<bx3_grid(), 64 * (BX_NC + BX_NL), lds, s>>>(p0, p1 ? *p1 : p0, p1 ? 1 : 0, bx3_pair_policy() ? 1 : 0);
     EAGCN_LAUNCH_CHECK();
     return EAGCN_OK;
 }
@@ -558,9 +549,6 @@ int launch_bx3(const BxProb& p0, const BxProb* p1, int np, hipStream_t s, double
     ProfScope ps(prof_tag, s, work);
     EAGCN_CHECK_ARG(!wide || !(p0.ep.Y || (p1 && p1->ep.Y)), "bx3 gemm: the 256 x 128 kernel has no BatchNorm tail pass (BxProb.ep)");
     if (wide) return launch_bx3w(p0, p1, np, s);
-    static const int dbg = [] { const char* e = getenv("EAGCN_BX3_DBG"); return e ? atoi(e) : 0; }();     // probes (wrong results!)
-    if (np == 3 && dbg == 1) return bx3_launch_cfg<3, 1>(p0, p1, s);
-    if (np == 3 && dbg == 2) return bx3_launch_cfg<3, 2>(p0, p1, s);
     return np == 3 ? bx3_launch_cfg<3>(p0, p1, s) : bx3_launch_cfg<1>(p0, p1, s);
 }
 

@@ -44,7 +44,6 @@ constexpr int BW_NW = 8;                                         // compute wave
 constexpr int BW_APL = BW_BM * 64, BW_BPL = BW_BN * 64;          // bytes of one plane image of a k-tile: 16 KB / 8 KB
 constexpr int BW_STAGE = 3 * (BW_APL + BW_BPL);                  // 72 KB
 constexpr int BW_NS = 2;                                         // 144 KB
-constexpr int BX3W_VAR_DEFAULT = 4;                                // DMAPOS 2, no priority flips (measured best of the five: profiles/r05_bx3w_variants.txt)
 static_assert(BW_APL / 1024 == 2 * BW_NW && BW_BPL / 1024 == BW_NW, "piece hand-out: two A pieces and one B piece per wave and plane");
 
 extern __shared__ __attribute__((aligned(1024))) unsigned char bw_smem[];
@@ -120,9 +119,8 @@ __device__ __forceinline__ BwStream bw_stream(const BxProb& p, int rot, int& rot
 
 // ---- one compute wave --------------------------------------------------------------------------------------------------------------------
 // wr = row block (0..3) of the 4 x 2 wave grid, G = column block = group (compile time: the two groups run differently rotated loops)
-template <bool TN, int NP, int G, int VAR, int DBG>
+template <bool TN, int NP, int G>
 __device__ __forceinline__ void bw_wave(const BxProb& p, const BwStream& st, const int wr) {
-    constexpr int PRIO = VAR & 1, DMAPOS = VAR >> 1;   // (A/B switches: EAGCN_BX3W_VAR)
     const int lane = threadIdx.x & 63;
     const int w8 = G * 4 + wr;                         // 0..7: which DMA pieces this wave requests
     // ---- LDS-DMA side: buffer descriptors (one per operand plane over the whole image), per-lane source offsets
@@ -182,7 +180,6 @@ __device__ __forceinline__ void bw_wave(const BxProb& p, const BwStream& st, con
         dsb = lds0 + (unsigned)(stage * BW_STAGE + w8 * 1024);
         dva0 = ok ? oa + rel_a0 : OOB; dva1 = ok ? oa + rel_a1 : OOB; dvb = ok ? ob + rel_b : OOB;
         oa += astep; ob += bstep; kposd += BW_BK; --leftd;
-        if constexpr (DBG == 1) dlive = false;         // (probe: no requests)
     };
     auto dma_piece = [&](const int i) __attribute__((always_inline)) {
         const int q = i / 3, r = i - 3 * q;
@@ -241,7 +238,6 @@ __device__ __forceinline__ void bw_wave(const BxProb& p, const BwStream& st, con
     bw_bf16x8 af[2][NP], bf[2][NP];
     // reads in the order the products below consume them: (a2, b0), (a1, b1), (a0, b2)
     auto load_set = [&](int stg, int s) __attribute__((always_inline)) {
-        if constexpr (DBG == 3) { if (stg >= 0) return; stg = 0; }      // (probe: no fragment reads inside the loop)
         const unsigned char* sa = bw_smem + stg * BW_STAGE;
         const unsigned char* sbp = sa + 3 * BW_APL;
 #pragma unroll
@@ -267,14 +263,6 @@ __device__ __forceinline__ void bw_wave(const BxProb& p, const BwStream& st, con
         if ((I1) < 3 * NP) dma_piece(I1);                                                                              \
         __builtin_amdgcn_sched_barrier(0);                                                                             \
     }
-        if constexpr (DBG == 2) {                      // (probe: no products; the fragments stay live)
-#pragma unroll
-            for (int q = 0; q < NP; ++q)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) { asm volatile("" ::"v"(af[t][q])); asm volatile("" ::"v"(bf[t][q])); }
-            if (with_dma) dma_all();
-            return;
-        }
         if constexpr (NP == 3) {
             EAGCN_BW_PROD(lo, 2, 0)
             EAGCN_BW_DMA2(0, 1)
@@ -343,20 +331,15 @@ __device__ __forceinline__ void bw_wave(const BxProb& p, const BwStream& st, con
     __builtin_amdgcn_s_barrier();                      // B_0: ... and everybody else's
     __builtin_amdgcn_sched_barrier(0);
     // barrier B_k+1: tile k + 1 has landed (every wave waited for its own pieces), nobody reads tile k's stage any more -> tile k + 2 may
-    // be requested.  WHERE the nine requests go (DMAPOS):
-    //   0  all nine right behind the barrier, both groups (first version)
-    //   1  G1: between the MFMAs of M(k,1), which it runs right behind the barrier; G0: as a block behind the reads R(k+1,0) (the reads'
-    //      latency covers part of the requests' issue time; G1 feeds the matrix pipe meanwhile)
-    //   2  G1 as 1; G0: between the MFMAs of M(k+1,0)
+    // be requested.  WHERE the nine requests go: between the MFMAs -- G1: of M(k,1), which it runs right behind the barrier; G0: of
+    // M(k+1,0) -- and no s_setprio around the MFMA blocks.  (Measured best of the placements tried -- all nine right behind the barrier;
+    // G0's as a block behind the reads R(k+1,0); either with priority flips: profiles/r05_bx3w_variants.txt.)
     auto sync_point = [&](int k) __attribute__((always_inline)) {
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        if (k + 2 < total) {
-            dma_prepare(k & 1);
-            if constexpr (DMAPOS == 0) dma_all();
-        }
+        if (k + 2 < total) dma_prepare(k & 1);
     };
     auto unit_end = [&]() __attribute__((always_inline)) {
         store_unit(un);
@@ -367,26 +350,20 @@ __device__ __forceinline__ void bw_wave(const BxProb& p, const BwStream& st, con
         } while (j < st.count && un.nk == 0);
         rem = un.nk;
     };
-    if constexpr (DBG == 3) load_set(-1, 0);
     for (int k = 0; k < total; ++k) {
         const int stage = k & 1;
         load_set(stage, 0);
-        if constexpr (G == 0 && DMAPOS == 1) { __builtin_amdgcn_sched_barrier(0); dma_all(); __builtin_amdgcn_sched_barrier(0); }
-        if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-        mma_set(G == 0 && DMAPOS == 2);
-        if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
+        mma_set(G == 0);
         load_set(stage, 1);
         if constexpr (G == 1) sync_point(k);
-        if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-        mma_set(G == 1 && DMAPOS != 0);
-        if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
+        mma_set(G == 1);
         if constexpr (G == 0) sync_point(k);
         if (--rem == 0) unit_end();
     }
 }
 
 // up to two problems in one persistent launch (the dX / dW pair of a layer's backward), as bx3_kernel
-template <int NP, int VAR, int DBG>
+template <int NP>
 __global__ __launch_bounds__(64 * BW_NW, 2) void bx3w_kernel(BxProb p0, BxProb p1, int has1, int pair_policy) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int rot = 0, rot1 = 0;
@@ -400,45 +377,30 @@ __global__ __launch_bounds__(64 * BW_NW, 2) void bx3w_kernel(BxProb p0, BxProb p
         const BwStream st = bw_stream(p, rot, rot1, ou, okt);
         rot = rot1;
         if (wave < 4) {
-            if (p.tn) bw_wave<true, NP, 0, VAR, DBG>(p, st, wave); else bw_wave<false, NP, 0, VAR, DBG>(p, st, wave);
+            if (p.tn) bw_wave<true, NP, 0>(p, st, wave); else bw_wave<false, NP, 0>(p, st, wave);
         } else {
-            if (p.tn) bw_wave<true, NP, 1, VAR, DBG>(p, st, wave - 4); else bw_wave<false, NP, 1, VAR, DBG>(p, st, wave - 4);
+            if (p.tn) bw_wave<true, NP, 1>(p, st, wave - 4); else bw_wave<false, NP, 1>(p, st, wave - 4);
         }
         // (no barrier between the passes: behind the last barrier of a pass no wave reads LDS any more -- sync_point waits for a wave's
         //  reads in front of every barrier -- so the next pass's first requests may overwrite both stages at once)
     }
 }
 
-template <int NP, int VAR, int DBG = 0>
+template <int NP>
 static int bx3w_launch_cfg(const BxProb& p0, const BxProb* p1, hipStream_t s) {
     constexpr int lds = BW_NS * BW_STAGE;
     static bool attr_done = false;
     if (!attr_done) {
-        EAGCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bx3w_kernel<NP, VAR, DBG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        EAGCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bx3w_kernel<NP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         attr_done = true;
     }
-    bx3w_kernel<NP, VAR, DBG><<<bx3_grid(), 64 * BW_NW, lds, s>>>(p0, p1 ? *p1 : p0, p1 ? 1 : 0, bx3_pair_policy() ? 1 : 0);
+    bx3w_kernel<NP><<<bx3_grid(), 64 * BW_NW, lds, s>>>(p0, p1 ? *p1 : p0, p1 ? 1 : 0, bx3_pair_policy() ? 1 : 0);
     EAGCN_LAUNCH_CHECK();
     return EAGCN_OK;
 }
 
 int launch_bx3w(const BxProb& p0, const BxProb* p1, int np, hipStream_t s) {
-    static const int var = [] { const char* e = getenv("EAGCN_BX3W_VAR"); return e ? atoi(e) : BX3W_VAR_DEFAULT; }();      // A/B switch: bit 0 s_setprio around the MFMA blocks, bits 1.. DMAPOS
-    static const int dbg = [] { const char* e = getenv("EAGCN_BX3W_DBG"); return e ? atoi(e) : 0; }();         // probes (wrong results!)
-    if (np == 3 && dbg == 1) return bx3w_launch_cfg<3, BX3W_VAR_DEFAULT, 1>(p0, p1, s);
-    if (np == 3 && dbg == 2) return bx3w_launch_cfg<3, BX3W_VAR_DEFAULT, 2>(p0, p1, s);
-    if (np == 3 && dbg == 3) return bx3w_launch_cfg<3, BX3W_VAR_DEFAULT, 3>(p0, p1, s);
-    if (np == 3) {
-        switch (var) {
-            case 0: return bx3w_launch_cfg<3, 0>(p0, p1, s);
-            case 1: return bx3w_launch_cfg<3, 1>(p0, p1, s);
-            case 2: return bx3w_launch_cfg<3, 2>(p0, p1, s);
-            case 3: return bx3w_launch_cfg<3, 3>(p0, p1, s);
-            case 4: return bx3w_launch_cfg<3, 4>(p0, p1, s);
-            default: return bx3w_launch_cfg<3, 5>(p0, p1, s);
-        }
-    }
-    return bx3w_launch_cfg<1, BX3W_VAR_DEFAULT>(p0, p1, s);
+    return np == 3 ? bx3w_launch_cfg<3>(p0, p1, s) : bx3w_launch_cfg<1>(p0, p1, s);
 }
 
 }  // namespace eagcn

@@ -218,6 +218,7 @@ static size_t carve_scratch(void* base, const eagcn_batch* b, const eagcn_model*
 
 static int check_model(const eagcn_batch* b, const eagcn_model* m, const char* who) {
     EAGCN_CHECK_ARG(b && m, "%s: null argument", who);
+    if (int rc = check_reserved_null(m->aux_stream, who, "eagcn_model.aux_stream")) return rc;
     EAGCN_CHECK_ARG(m->n_layers >= 1 && m->n_layers <= 4, "%s: n_layers=%d", who, m->n_layers);
     const eagcn_head_params* h = &m->head;
     EAGCN_CHECK_ARG(h->f_in >= 1 && h->n_den1 >= 1 && h->n_den2 >= 1 && h->nclass >= 1, "%s: bad head sizes", who);
@@ -249,7 +250,7 @@ static eagcn_layout out_layout(const eagcn_layer_params* p) {
 // the top layer's output matrix is not built in the forward (eagcn_model.fuse_readout): Concate only -- its non-stored rows are
 // masked to zero, so the read-out sums nothing but packed rows
 static bool fused_readout(const eagcn_model* m) {
-    static const bool env = [] { const char* v = getenv("EAGCN_NO_FUSED_READOUT"); return !(v && v[0] == '1'); }();
+    static const bool env = !env_flag("EAGCN_NO_FUSED_READOUT", false);
     return env && m->fuse_readout && m->layer[m->n_layers - 1].structure == EAGCN_STRUCT_CONCATE;
 }
 
@@ -260,12 +261,12 @@ static bool fused_readout(const eagcn_model* m) {
 static bool top_bn_sums(const eagcn_batch* b, const eagcn_model* m) {
     if (!top_bn_sums_enabled() || m->n_layers < 1 || !fused_readout(m) || !m->training || m->stats_hook) return false;
     if (m->molfp_mode != 0 && m->molfp_mode != 1) return false;
-    return layer_top_sums_route(b, &m->layer[m->n_layers - 1], m->aux_stream != nullptr);
+    return layer_top_sums_route(b, &m->layer[m->n_layers - 1]);
 }
 
 // layer l's output is needed as plane images only: it has them, and the layer above reads nothing else (forward and backward)
 static bool hidden_planes_only(const eagcn_batch* b, const eagcn_model* m, const ModelSaved& sv, int l) {
-    return l + 1 < m->n_layers && sv.L[l].xout_planes && layer_reads_planes_only(b, &m->layer[l + 1], m->aux_stream != nullptr);
+    return l + 1 < m->n_layers && sv.L[l].xout_planes && layer_reads_planes_only(b, &m->layer[l + 1]);
 }
 
 }  // namespace eagcn
@@ -283,6 +284,7 @@ extern "C" size_t eagcn_model_scratch_bytes(const eagcn_batch* b, const eagcn_mo
 extern "C" int eagcn_model_atom_rep(const eagcn_batch* b, const eagcn_model* m, size_t* xout_offset,
                                     size_t* pad_row_offset, int* ld) {
     EAGCN_CHECK_ARG(b && m && xout_offset && pad_row_offset && ld, "eagcn_model_atom_rep: null argument");
+    RC(check_reserved_null(m->aux_stream, "eagcn_model_atom_rep", "eagcn_model.aux_stream"));
     ModelSaved s;
     carve_saved(nullptr, b, m, &s);
     *xout_offset = s.xout_last_off;
@@ -294,6 +296,7 @@ extern "C" int eagcn_model_atom_rep(const eagcn_batch* b, const eagcn_model* m, 
 extern "C" int eagcn_model_atom_rep_materialize(const eagcn_batch* b, const eagcn_model* m, void* saved, size_t saved_bytes,
                                                  void* stream) {
     EAGCN_CHECK_ARG(b && m && saved, "eagcn_model_atom_rep_materialize: null argument");
+    RC(check_reserved_null(m->aux_stream, "eagcn_model_atom_rep_materialize", "eagcn_model.aux_stream"));
     if (!fused_readout(m)) return EAGCN_OK;                  // the forward built the matrix itself
     ModelSaved sv;
     EAGCN_CHECK_ARG(carve_saved(saved, b, m, &sv) <= saved_bytes, "eagcn_model_atom_rep_materialize: saved block too small");
@@ -308,6 +311,7 @@ extern "C" int eagcn_model_atom_rep_materialize(const eagcn_batch* b, const eagc
 extern "C" int eagcn_model_pack_input(const eagcn_batch* b, const eagcn_model* m, const float* afm, void* saved,
                                       size_t saved_bytes, void* stream) {
     EAGCN_CHECK_ARG(b && m && afm && saved, "eagcn_model_pack_input: null argument");
+    RC(check_reserved_null(m->aux_stream, "eagcn_model_pack_input", "eagcn_model.aux_stream"));
     ModelSaved sv;
     EAGCN_CHECK_ARG(carve_saved(saved, b, m, &sv) <= saved_bytes, "eagcn_model_pack_input: saved block too small");
     return eagcn_pack_rows(b, afm, layout_width(&m->layer[0].in), &m->layer[0].in, sv.x0, stream);
@@ -706,7 +710,6 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
                                void* scratch, size_t scratch_bytes, const float* dout, const float* dgraph_rep,
                                const eagcn_layer_grads* lg, const eagcn_head_grads* hg, int with_head, int layer_hi, int layer_lo,
                                float* dx0, bool input_only, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
     EAGCN_CHECK_ARG(saved && scratch && dout && (lg || input_only) && hg, "eagcn_model_backward: null buffer");
     EAGCN_CHECK_ARG(hg->d_den1_w && hg->d_den2_w && hg->d_den3_w && hg->d_gbn_w && hg->d_gbn_b && hg->d_bn1_w &&
                         hg->d_bn1_b && hg->d_bn2_w && hg->d_bn2_b, "eagcn_model_backward: null head gradient");
@@ -721,8 +724,6 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
     const int F = m->head.f_in;
     // (no clearing launch: the forward call left the hand-off flags and the backward sums zero; owners reset their flags)
     const ZeroJob zb{nullptr, 0, sc.hsb, sc.n_hst};
-    hipStream_t side = m->aux_stream ? (hipStream_t)m->aux_stream : s;
-    const bool forked = side != s;
     const eagcn_layer_params* last = &m->layer[m->n_layers - 1];
     const eagcn_layout lay = out_layout(last);
     const bool weighted = last->structure == EAGCN_STRUCT_WEIGHTED;
@@ -738,7 +739,7 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
     rgd.dg = sc.dg; rgd.F = F; rgd.size = size; rgd.mode = m->molfp_mode; rgd.map = make_colmap(&lay);
     const int top_l = m->n_layers - 1;
     // a hidden Concate layer's dH and BatchNorm column sums come out of the dX product of the plane-pair layer above it, when both
-    // run in this call (layer.hip layer_hidden_sums_route; training, local BatchNorm, one stream): `fused` = the layer about to run
+    // run in this call (layer.hip layer_hidden_sums_route; training, local BatchNorm): `fused` = the layer about to run
     // finds them in its upstream buffer and in sc.hid_slab
     BxBnEpi below;
     bool fused = false;
@@ -757,7 +758,6 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
         w.x = l == 0 ? sv.x0 : (hidden_planes_only(b, m, sv, l - 1) ? nullptr : sv.L[l - 1].xout);
         w.P = L.P; w.Y = L.Y; w.rscale = L.rscale; w.bn = L.bn; w.xout = L.xout; w.pad_row = L.pad_row;
         w.scratch = sc.layer; w.scratch_bytes = sc.layer_bytes; w.packed = L.packed; w.packed_bytes = L.packed_bytes;
-        w.aux_stream = m->aux_stream;
         w.stats_hook = m->stats_hook; w.stats_user = m->stats_user;
         w.x_planes = l > 0 ? sv.L[l - 1].xout_planes : nullptr;
         const bool top = l == top_l;
@@ -775,7 +775,7 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
         if (fused) { o.dh_sums = sc.hid_slab; o.dh_nslab = hidden_bn_slabs(b->T); }
         bool carried = false;
         fused = l > layer_lo && !input_only && m->training && !m->stats_hook &&
-                layer_hidden_sums_route(b, &m->layer[l], &m->layer[l - 1], m->aux_stream != nullptr, &below);
+                layer_hidden_sums_route(b, &m->layer[l], &m->layer[l - 1], &below);
         if (fused) {
             below.Y = sv.L[l - 1].Y; below.bn = sv.L[l - 1].bn; below.row_m = b->row_m; below.slab = sc.hid_slab;
             o.below = &below; o.below_done = &carried;
@@ -787,7 +787,6 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
         fused = fused && carried;                                // (the layer's real plan decides: layer.hip bwd_products)
         EAGCN_CHECK_ARG(!fused || !pend_in.eacc, "eagcn_model_backward: a plane-pair layer handed its edge reduction down");
     }
-    if (forked) RC(stream_after(s, side));                       // join: every gradient is complete on s
     return EAGCN_OK;
 }
 

@@ -798,7 +798,7 @@ static int head_nw(int want, int tiles) {
         return n;
     }();
     if (want == 4 || want == 8) return want;
-    static const int env = [] { const char* e = getenv("EAGCN_HEAD_NW"); return e ? atoi(e) : 0; }();
+    static const int env = env_int("EAGCN_HEAD_NW", 0);
     if (env == 4 || env == 8) return env;
     // (round 6: eight waves up to TWO workgroups per CU -- dense 1's backward at 256 molecules is 352 tiles -- measured -1 % at
     //  configs[1] while the side stream's index build was held back behind the forward, and +1.6 % (0.366 -> 0.372 ms) once it was
@@ -832,7 +832,7 @@ int head_bwd(const HeadBwd& a, hipStream_t s) {
     const uintptr_t al = reinterpret_cast<uintptr_t>(a.dy) | reinterpret_cast<uintptr_t>(a.W) | reinterpret_cast<uintptr_t>(a.y) |
                          reinterpret_cast<uintptr_t>(a.extra);
     const bool vec = (a.N & 3) == 0 && (al & 15) == 0;
-    static const int light_env = [] { const char* e = getenv("EAGCN_HEAD_LIGHT"); return e ? atoi(e) : 1; }();     // rounds (of 2 workgroups per CU) from which the light kernel is taken; 0: never
+    static const int light_env = env_int("EAGCN_HEAD_LIGHT", 1);     // rounds (of 2 workgroups per CU) from which the light kernel is taken; 0: never
     const bool light = light_env > 0 && nw == 4 && a.nw == 0 && tiles > 2 * light_env * head_cus();
 #define EAGCN_HB(V, D) do { if (nw == 8) head_bwd_kernel<V, D, 8><<<tiles, 512, lds, s>>>(a); else if (light && V) head_bwd_light_kernel<D><<<tiles, 256, lds, s>>>(a); \
                             else head_bwd_kernel<V, D, 4><<<tiles, 256, lds, s>>>(a); } while (0)
@@ -846,7 +846,7 @@ int head_bwd(const HeadBwd& a, hipStream_t s) {
 }
 // the fused middle launch needs a row block of the logits to be one tile
 bool head_mid_ok(int n2, int nclass) {
-    static const bool env = [] { const char* v = getenv("EAGCN_HEAD_FUSED"); return !(v && v[0] == '0'); }();
+    static const bool env = env_flag("EAGCN_HEAD_FUSED", true);
     const size_t lds = (size_t)(HT_RED + 20 * ((n2 + 3) & ~3) + 35 * ((nclass + 3) & ~3) + n2 * nclass + 4) * sizeof(float);
     return env && nclass <= 64 && lds <= 150 * 1024;
 }

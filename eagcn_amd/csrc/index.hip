@@ -829,7 +829,7 @@ extern "C" int eagcn_index_build(const float* adj, const float* const* rel, eagc
     const int nit = cdiv((Nin + 15) / 16 * 16, 256);
     EAGCN_CHECK_ARG(nit <= 4, "eagcn_index_build: N=%d exceeds the supported 1024 atoms", b->N);
     // streaming scan: 16-byte adjacency loads, several rows per wave, the channel gather of a wave's bonds batched over its lanes
-    static const bool scan4 = [] { const char* v = getenv("EAGCN_SCAN4"); return !(v && v[0] == '0'); }();
+    static const bool scan4 = env_flag("EAGCN_SCAN4", true);
     if (scan4) {
         // widest aligned adjacency load the row stride and the base pointer allow
         const uintptr_t ap = reinterpret_cast<uintptr_t>(adj);

@@ -85,7 +85,6 @@ constexpr int EDGE_SLAB = 264;
 constexpr int EDGE_COPIES = 8;
 inline size_t edge_acc_bytes() { return align256((size_t)EDGE_COPIES * EAGCN_MAX_VIEWS * EDGE_SLAB * sizeof(double)); }
 int edge_grid_x(const eagcn_batch* b);
-int launch_edge_grad(const EdgeArgs& a, hipStream_t s);
 int launch_agg_edge(AggArgs a, const EdgeArgs& e, hipStream_t s);   // transposed aggregation + edge gradients, one grid
 
 enum { BN_SC = 0, BN_SH, BN_MU, BN_INV };     // rows of a layer's [4][Fp] BatchNorm coefficient table
@@ -306,10 +305,10 @@ struct LayerBwdOpts {
 // would the backward of layer `up` (with d(input)) run its products as the plane pair, and that
 // of the Concate layer `low` below it store dH in a reduction pass and leave the second pass to lagg.hip -- the pass the dX units'
 // tail pass replaces (on the 128 x 128 kernel: bwd_products)?  Fills what of *ep is the layer's own (dropout, widths); the caller adds Y', the table, the mask and the slabs.
-bool layer_hidden_sums_route(const eagcn_batch* b, const eagcn_layer_params* up, const eagcn_layer_params* low, bool aux_stream, BxBnEpi* ep);
+bool layer_hidden_sums_route(const eagcn_batch* b, const eagcn_layer_params* up, const eagcn_layer_params* low, BxBnEpi* ep);
 inline int hidden_bn_slabs(int T) { return (T > 0 ? T + BX_EPI_ROWS - 1 : BX_EPI_ROWS) / BX_EPI_ROWS; }      // slab capacity for T packed rows
 // would the backward of top layer p (per-molecule upstream gradient) take the route that top_sums replaces a pass of?  (layer.hip)
-bool layer_top_sums_route(const eagcn_batch* b, const eagcn_layer_params* p, bool aux_stream);
+bool layer_top_sums_route(const eagcn_batch* b, const eagcn_layer_params* p);
 bool top_bn_sums_enabled();                  // eagcn_set_top_bn_sums != 0
 bool top_bn_gather_enabled();                // ... == 1: the staging gathers dg per molecule (2: rows of the read-out gradient are written)
 int layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const float* dxout,
@@ -333,7 +332,12 @@ int layer_forward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const 
                        bool prepacked, bool skip_apply = false, bool planes_only = false);
 // true when BOTH directions of layer p take their input x from its bf16 plane images and never from the fp32 matrix (the route
 // layer.hip plans for a call that brings the planes); a layer that is then handed w->x == nullptr fails loudly if it reaches a fallback
-bool layer_reads_planes_only(const eagcn_batch* b, const eagcn_layer_params* p, bool aux_stream);
+bool layer_reads_planes_only(const eagcn_batch* b, const eagcn_layer_params* p);
+// eagcn_layer_bufs.aux_stream / eagcn_model.aux_stream are reserved (the backward runs on the call's one stream): a value is refused
+inline int check_reserved_null(const void* value, const char* who, const char* field) {
+    EAGCN_CHECK_ARG(!value, "%s: %s is reserved and must be null", who, field);
+    return EAGCN_OK;
+}
 // relu / dropout / mask / view merge of a layer from its saved Y and BatchNorm table (what layer_forward_impl ends with)
 int layer_apply_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, void* stream);
 int pack_params_all(const eagcn_batch* b, const eagcn_layer_params* const* ps, void* const* packed,

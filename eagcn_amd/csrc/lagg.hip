@@ -25,7 +25,7 @@
 // dense block to multiply).
 // Backward (one kernel): the transposed aggregation dP[j,:] = sum_{bonds (i,j)} s_i sigma_ij dY'[i,:] + s_j r dY'[j,:] + 1e-9 (G_b -
 // sum_{bonds} s_i dY'[i,:]), G_b = sum_i s_i dY'[i,:], s_i = m_i / rowsum_i -- and, from the SAME gathers, the edge gradients of
-// agg.hip's edge_grad_kernel: with dY' of the block in LDS, row j's own P and Y' rows in registers,
+// agg.hip's edge_grad_body: with dY' of the block in LDS, row j's own P and Y' rows in registers,
 //     dA^[i,j] = <dY'[i,:], P[j,:]> ,  rowdot_i = <dY'[i,:], Y'[i,:]> ,  dU[i,j] = s_i (dA^[i,j] - rowdot_i)
 // are partial sums over the workgroup's 32 columns (everything is linear in them): d w_k[c] += dU s (1 - s) by bond type through an
 // LDS histogram, d self_r from the diagonal, flushed with fp64 atomics into the shared accumulator slabs (kernels.h EDGE_COPIES).
@@ -74,18 +74,18 @@ static int lagg_policy() {
     return v;
 }
 static int lagg_min_n() {
-    static const int v = [] { const char* e = getenv("EAGCN_LAGG_MIN_N"); return e ? atoi(e) : 240; }();
+    static const int v = env_int("EAGCN_LAGG_MIN_N", 240);
     return v;
 }
 static int lagg_fwd_maxb() {
     // (round 6: no limit by default.  Up to round 5 batches of more than 256 small molecules took the matrix-core forward of agg.hip;
     //  measured again with this round's kernels the step is equal or faster on this path -- Tox21 B = 1024 0.828 -> 0.822 ms, Lipo
     //  1.254 -> 1.258 -- and the default forward no longer sums the 1e-9 filler products one by one in fp32)
-    static const int v = [] { const char* e = getenv("EAGCN_LAGG_FWD_MAXB"); return e ? atoi(e) : 0x7FFFFFFF; }();
+    static const int v = env_int("EAGCN_LAGG_FWD_MAXB", 0x7FFFFFFF);
     return v;
 }
 bool lagg_wfuse() {
-    static const bool on = [] { const char* v = getenv("EAGCN_LAGG_WFUSE"); return !(v && v[0] == '0'); }();
+    static const bool on = env_flag("EAGCN_LAGG_WFUSE", true);
     return on;
 }
 // should the index of batches of this shape carry bond lists and row blocks?  structure: EAGCN_STRUCT_* of the layers, or -1 (not known)
@@ -96,7 +96,7 @@ bool lagg_wanted(int B, int N, int structure) {
     return N >= lagg_min_n() || B <= lagg_fwd_maxb() || structure != EAGCN_STRUCT_WEIGHTED || lagg_wfuse();
 }
 int lagg_parts() {                                    // (debug switch) bit 0: forward, bit 1: backward on this path
-    static const int v = [] { const char* e = getenv("EAGCN_LAGG_PARTS"); return e ? atoi(e) : 3; }();
+    static const int v = env_int("EAGCN_LAGG_PARTS", 3);
     return v;
 }
 // does this batch take the path?  dir 0: forward, 1: backward; absorbs_bn: the layer's BatchNorm backward would leave its second pass here
@@ -117,7 +117,7 @@ bool lagg_use(const eagcn_batch* b, int dir, bool absorbs_bn, const ViewCols* vc
 // to hide a block's barrier-separated phases) lose: a block's fixed cost (eight clamped row loads per thread whatever the row count, the
 // record pass, four barriers) is what a launch pays per block, and the per-molecule column sums stop being shared.
 int lagg_block_rows(const eagcn_batch* b) {
-    static const int fixed = [] { const char* e = getenv("EAGCN_LAGG_RB"); return e ? atoi(e) : 0; }();
+    static const int fixed = env_int("EAGCN_LAGG_RB", 0);
     (void)b;
     return fixed > 0 ? std::min(fixed, LAGG_RB) : LAGG_RB;
 }
@@ -138,8 +138,8 @@ static void lagg_extent(const eagcn_batch& bt, const ViewCols& vc, int* chunks, 
 // workgroups as it can get: configs[1], B = 1024 and Lipo measured 3-5 % SLOWER with more), several where there are thousands (C5:
 // 41 k, HIV widths: 26 k / 10 k): forward up to 8 (C5 forward 681 -> 593 us), transposed up to 4 (C5 -2 %, HIV: no difference between 1, 4, 8)
 static int lagg_cpw(const eagcn_batch& bt, const ViewCols& vc, bool trans) {
-    static const int cpw_env = [] { const char* e = getenv("EAGCN_LAGG_CPW"); return e ? atoi(e) : 0; }();
-    static const int cpw_bwd = [] { const char* e = getenv("EAGCN_LAGG_CPW_BWD"); return e ? atoi(e) : 1; }();
+    static const int cpw_env = env_int("EAGCN_LAGG_CPW", 0);
+    static const int cpw_bwd = env_int("EAGCN_LAGG_CPW_BWD", 1);
     int chunks, gy;
     lagg_extent(bt, vc, &chunks, &gy);
     const long wgs = (long)vc.K * chunks * gy;
@@ -163,8 +163,6 @@ int launch_lagg_fwd(AggArgs a, hipStream_t s) {
     ProfScope ps(PROF_AGG, s);
     EdgeArgs e;
     memset(&e, 0, sizeof(e));
-    static const int dbgm = [] { const char* e = getenv("EAGCN_LAGG_DBG"); return e ? atoi(e) : 0; }();
-    a.xcd = dbgm;
     if (a.cpw > 1) lagg_kernel<false, true><<<grid, 256, 0, s>>>(a, e);
     else lagg_kernel<false, false><<<grid, 256, 0, s>>>(a, e);
     EAGCN_LAUNCH_CHECK();
@@ -178,8 +176,6 @@ int launch_lagg_bwd(AggArgs a, const EdgeArgs& e, hipStream_t s, bool edge) {
     int rc = lagg_grid(a, &grid, &a.nchunk, &a.cpw, true);
     if (rc) return rc;
     ProfScope ps(PROF_AGG, s);
-    static const int dbgm = [] { const char* e = getenv("EAGCN_LAGG_DBG"); return e ? atoi(e) : 0; }();
-    a.xcd = dbgm;
     EAGCN_CHECK_ARG(!a.w_aw || a.bn_tab, "lagg: the upstream-gradient form needs the BatchNorm tables");
     EAGCN_CHECK_ARG(!a.w_rowm || a.bn_tab, "lagg: the row-mask staging needs the BatchNorm tables");
     if (!edge) {

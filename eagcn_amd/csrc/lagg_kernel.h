@@ -125,7 +125,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
     const uint64_t* codes = TRANS ? bt.tcode : bt.ecode;
     if constexpr (TE) { h_s[tid] = 0.0; if (tid < 8) h_s[256 + tid] = 0.0; }
     double dr_acc = 0.0;
-    const int dbg = a.xcd;                                            // (probe mask, EAGCN_LAGG_DBG: wrong results)
     const int4* rinfo = reinterpret_cast<const int4*>(bt.row_info);
     // transposed with the BatchNorm backward's second pass folded in (AggArgs.bn_tab): this lane's five per-column constants
     const bool fuse_bn = TRANS && a.bn_tab != nullptr;
@@ -236,7 +235,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
             //          forward      y_i  = sum_e w_e P[src_e] + (sc r m_i) P[i] + (sc 1e-9) S_b
             //          transposed   dP_j = sum_e w_e Z[src_e] + (r s_j) Z[j] + 1e-9 G_b ,   d w[code_e] += h_e (<Z[src_e], P_j> - rowdot_src)
             //      the row loop is two or three LDS reads, five gathers and a few dozen FMAs without a branch.
-            const int first = pt.x - E0, cnt = (dbg & 2) ? 0 : pt.y;
+            const int first = pt.x - E0, cnt = pt.y;
             if (tid < rows) {
                 float we[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, he[TRANS ? 8 : 1] = {0.f};
                 uint32_t srcs = 0u, cds = 0u, srcs2 = 0u, cds2 = 0u, slow = cnt > 8 ? LG_SLOW : 0u;
@@ -443,7 +442,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
         //      of them read from LDS in ONE batch, then added up in registers (row by row behind the data-dependent molecule test the
         //      reads cost 4 us of an 18 us launch at configs[1]; contiguous OWNERSHIP of rows -- sums straight from the staging
         //      registers -- puts the eight groups of a wave on the same banks in every other phase: C5 11.0 -> 12.2 ms)
-        if (!(dbg & 1)) {
+        {
             const int per = (rows + LG_G - 1) / LG_G, ra = g * per;
             int mu[LG_U];
             float wu[TRANS ? LG_U : 1];
@@ -546,9 +545,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
                 s1[1] += (double)y.y; s2[1] += (double)y.y * (double)y.y;
                 s1[2] += (double)y.z; s2[2] += (double)y.z * (double)y.z;
                 s1[3] += (double)y.w; s2[3] += (double)y.w * (double)y.w;
-                if (col_ok && !(dbg & 4)) *reinterpret_cast<float4*>(a.dst + (size_t)(R0 + rr) * a.ldd + c0) = y;
+                if (col_ok) *reinterpret_cast<float4*>(a.dst + (size_t)(R0 + rr) * a.ldd + c0) = y;
             } else {
-                if (col_ok && !(dbg & 4)) {
+                if (col_ok) {
                     int cs = c0;
                     asm volatile("" : "+v"(cs));                      // (no per-lane 64-bit store bases held across the block loop)
                     if (a.planes.p) bx_store4(a.planes, R0 + rr, cs, y);

@@ -1008,11 +1008,11 @@ enum Bn2 {
                                  // no reduction pass, no stored dH; lagg_top.hip re-forms dH from the read-out gradient, gathered per
                                  // molecule (LayerBwdOpts.top_dge) or written out as rows first (rows_late)
 };
-enum EdgePath { EDGE_NONE = 0, EDGE_WITH_LAGG, EDGE_COLAUNCH, EDGE_SEPARATE };   // lagg.hip's gathers | one grid with agg.hip | own launch
+enum EdgePath { EDGE_NONE = 0, EDGE_WITH_LAGG, EDGE_COLAUNCH };   // lagg.hip's gathers | one grid with agg.hip (3, an own launch: retired)
 enum BwdProd {
     BWD_NONE = 0, BWD_PLANES_PAIR, BWD_PLANES_DW, BWD_PLANES_DX,      // gemm_bx3.hip: dX with dW | dW alone | dX alone (input-only)
     BWD_G3_XK, BWD_G3_SCATTER,   // gemm3.hip pair: dW as one partial slab per XCD | written straight into the per-view gradients
-    BWD_TILED_PAIR, BWD_TILED_SEPARATE, BWD_TILED_DX,                 // gemm.hip: one grid | dW on the side stream, then dX | dX alone
+    BWD_TILED_PAIR, BWD_TILED_SEPARATE, BWD_TILED_DX,                 // gemm.hip: one grid | dW alone (no dX asked) | dX alone
     BWD_REFUSED
 };
 struct PlanAsk {
@@ -1039,25 +1039,12 @@ struct LayerRoute {
 };
 
 // the switches (each read once).  EAGCN_AGG / EAGCN_LAGG_*: lagg.hip; EAGCN_GEMM_X6: gemm.hip; EAGCN_GEMM3_XK: gemm3.hip
-static bool env_is(const char* name, char c) { const char* v = getenv(name); return v && v[0] == c; }
-#define EAGCN_SWITCH(fn, expr) static bool fn() { static const bool on = (expr); return on; }
-EAGCN_SWITCH(sw_gemm3, !env_is("EAGCN_NO_GEMM3", '1'))
-EAGCN_SWITCH(sw_planes_only, !env_is("EAGCN_PLANES_ONLY", '0'))
-EAGCN_SWITCH(sw_lagg_fuses_bn, !env_is("EAGCN_LAGG_FUSE_BN", '0'))        // 0: lagg.hip never absorbs the BatchNorm backward's second pass
-EAGCN_SWITCH(sw_edge_atomic, !env_is("EAGCN_EDGE_SLABS", '1'))
-EAGCN_SWITCH(sw_rows_first, !env_is("EAGCN_W_ROWS_FIRST", '0'))
-EAGCN_SWITCH(sw_colaunch, !env_is("EAGCN_NO_COLAUNCH", '1'))
-EAGCN_SWITCH(sw_pair, !env_is("EAGCN_NO_PAIR", '1'))
-EAGCN_SWITCH(sw_edge_defer, !env_is("EAGCN_NO_EDGE_DEFER", '1'))
-#undef EAGCN_SWITCH
+static bool sw_gemm3() { static const bool on = !env_flag("EAGCN_NO_GEMM3", false); return on; }
+static bool sw_planes_only() { static const bool on = env_flag("EAGCN_PLANES_ONLY", true); return on; }
 // EAGCN_BWD_STORE_DH=1 / 0 forces the elementwise / the re-forming second pass (default: Bn2 above)
 static bool bn_bwd_two_pass(bool weighted) {
-    static const int force = [] { const char* v = getenv("EAGCN_BWD_STORE_DH"); return v ? (v[0] == '1' ? 1 : 0) : -1; }();
+    static const int force = getenv("EAGCN_BWD_STORE_DH") ? (env_flag("EAGCN_BWD_STORE_DH", false) ? 1 : 0) : -1;
     return force < 0 ? weighted : force == 0;
-}
-static int bn_apply_map() {
-    static const int v = [] { const char* e = getenv("EAGCN_BN_APPLY_MAP"); return e ? atoi(e) : -1; }();
-    return v;
 }
 // Which layers run their products on the wave-autonomous balanced kernel (gemm3.hip): the hidden layers.  The first
 // layer (24 atom features) is a different animal: its forward product has two k-steps per tile and its weight gradient
@@ -1070,10 +1057,10 @@ static bool gemm3_layer(int ld_in) {
 static LayerRoute plan_layer(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const LayerDims& d,
                              PlanAsk ask) {
     LayerRoute r;
-    const bool wt = p->structure == EAGCN_STRUCT_WEIGHTED, forked = w->aux_stream != nullptr;
+    const bool wt = p->structure == EAGCN_STRUCT_WEIGHTED;
     bool general = false;                             // (code books: the edge reduction reads a view's whole histogram per channel)
     for (int k = 0; k < p->K; ++k) general = general || b->rel_vec[k] != nullptr;
-    r.edge_atomic = sw_edge_atomic() && !general;
+    r.edge_atomic = !general;
     r.store_dh = !bn_bwd_two_pass(wt);
     if (b->T <= 0) return r;                          // no packed row: no product, no aggregation, a row-less reduction
     r.fwd_agg = fwd_agg_lagg(b, d.vc) ? AGG_LAGG : AGG_DENSE;
@@ -1096,8 +1083,8 @@ static LayerRoute plan_layer(const eagcn_batch* b, const eagcn_layer_params* p, 
     // The LDS-staged kernel runs the transposed aggregation + edge gradients (which must then leave through the shared
     // accumulators).  It absorbs the second pass of the BatchNorm backward: of a Concate layer from the stored dH, of a Weighted_sum
     // layer from the upstream gradient; input-only: no edge gradients to route, and the staging absorbs whatever the structure
-    const bool fuse_w = bn_bwd_two_pass(wt) && wt && sw_lagg_fuses_bn() && lagg_wfuse();
-    const bool absorbs = sw_lagg_fuses_bn() && (!bn_bwd_two_pass(wt) || (wt && lagg_wfuse()));
+    const bool fuse_w = bn_bwd_two_pass(wt) && wt && lagg_wfuse();
+    const bool absorbs = !bn_bwd_two_pass(wt) || (wt && lagg_wfuse());
     const bool lagg = ask.input_only ? lagg_use(b, 1, true) : (r.edge_atomic && lagg_use(b, 1, absorbs));
     r.bwd_agg = lagg ? AGG_LAGG : AGG_DENSE;
     if (ask.input_only && !p->training) {
@@ -1109,10 +1096,9 @@ static LayerRoute plan_layer(const eagcn_batch* b, const eagcn_layer_params* p, 
         // lagg.hip wants a per-molecule read-out gradient as ROWS ([T][ldo], K times narrower than dH) -- written first, so that the
         // reduction reads them with 16-byte loads as well instead of gathering dg[molecule] element by element
         r.bn2 = BN2_STAGED_FROM_UPSTREAM;
-        r.rows_first = ask.mol_grad && sw_rows_first();
-        r.rows_late = ask.mol_grad && !r.rows_first;
+        r.rows_first = ask.mol_grad;
     } else if (bn_bwd_two_pass(wt)) r.bn2 = BN2_REDUCE_APPLY;
-    else r.bn2 = (lagg && sw_lagg_fuses_bn()) ? BN2_STAGED_FROM_DH : BN2_ELEMENTWISE;
+    else r.bn2 = lagg ? BN2_STAGED_FROM_DH : BN2_ELEMENTWISE;
     if (ask.top_sums && r.bn2 == BN2_STAGED_FROM_DH && ask.mol_grad && !wt) {
         // the sums are there already; the staging gathers the read-out gradient per molecule, or reads it as rows (as wide as dH,
         // never dH itself) written behind the finalize
@@ -1124,18 +1110,18 @@ static LayerRoute plan_layer(const eagcn_batch* b, const eagcn_layer_params* p, 
     // dH and its sums were formed by the dX product of the layer above: the one route whose pass that replaces (dH stored by the
     // pass, the second pass in lagg.hip's staging -- which then stages from the upstream buffer)
     r.dh_given = ask.dh_given && r.bn2 == BN2_STAGED_FROM_DH && r.store_dh && !wt && !ask.mol_grad && !ask.input_only;
-    const bool planes = d.np && !forked && bx3_ok(bq.bw) && (!ask.has_dx || bx3_ok(bq.bx));
+    const bool planes = d.np && bx3_ok(bq.bw) && (!ask.has_dx || bx3_ok(bq.bx));
     r.bwd_split_x = planes && !w->x_planes && !ask.input_only;
     if (ask.input_only) r.bwd_prod = planes ? BWD_PLANES_DX : BWD_TILED_DX;
     else if (!planes && !w->x) r.bwd_prod = BWD_REFUSED;
     if (r.bwd_prod != BWD_NONE) return r;
-    r.edge = (lagg && r.edge_atomic) ? EDGE_WITH_LAGG : (!forked && sw_colaunch()) ? EDGE_COLAUNCH : EDGE_SEPARATE;
+    r.edge = (lagg && r.edge_atomic) ? EDGE_WITH_LAGG : EDGE_COLAUNCH;
     if (planes) r.bwd_prod = ask.has_dx ? BWD_PLANES_PAIR : BWD_PLANES_DW;
-    else if (!forked && ask.has_dx && gemm3_layer(d.ld_in) && gemm3_ok(gq.gw) && gemm3_ok(gq.gx))
+    else if (ask.has_dx && gemm3_layer(d.ld_in) && gemm3_ok(gq.gw) && gemm3_ok(gq.gx))
         r.bwd_prod = gemm3_xk_enabled() ? BWD_G3_XK : BWD_G3_SCATTER;
-    else r.bwd_prod = (ask.has_dx && !forked && sw_colaunch() && sw_pair()) ? BWD_TILED_PAIR : BWD_TILED_SEPARATE;
+    else r.bwd_prod = ask.has_dx ? BWD_TILED_PAIR : BWD_TILED_SEPARATE;
     // nothing but the edge reduction is left for this layer (no dW slabs to sum): the next layer's first backward kernel does it
-    r.defer_drain = sw_edge_defer() && ask.has_drain_out && r.edge_atomic && r.bwd_prod == BWD_G3_SCATTER && !forked;
+    r.defer_drain = ask.has_drain_out && r.edge_atomic && r.bwd_prod == BWD_G3_SCATTER;
     return r;
 }
 
@@ -1149,7 +1135,7 @@ static int apply_launch(const eagcn_batch* b, const eagcn_layer_params* p, const
     aa.do_drop = dr.on; aa.thr = dr.thr; aa.inv_keep = dr.inv_keep; aa.seed = dr.seed; aa.seed_dev = dr.seed_dev;
     aa.planes = BxOut{gemm_planes() ? w->xout_planes : nullptr, bx_plane_elems(b->T, d.ldo), gemm_planes(), b->T};
     if (planes_only && aa.planes.p) aa.out = nullptr;        // (the only reader is the layer above, through the planes)
-    aa.tile_map = bn_apply_map() >= 0 ? bn_apply_map() : (aa.planes.p ? 1 : 0);
+    aa.tile_map = aa.planes.p ? 1 : 0;
     const size_t nthr = aa.tile_map ? (size_t)cdiv(std::max(b->T, 1), 8) * cdiv(d.ldo, 32) * 64 : (size_t)std::max(b->T, 1) * d.ldo / 4;
     bn_apply_kernel<<<ew_grid(nthr), 256, 0, s>>>(aa);
     EAGCN_LAUNCH_CHECK();
@@ -1180,10 +1166,12 @@ extern "C" int eagcn_layer_route(const eagcn_batch* b, const eagcn_layer_params*
     int rc = check_layer(b, p, "eagcn_layer_route");
     if (rc) return rc;
     EAGCN_CHECK_ARG(w && out, "eagcn_layer_route: null argument");
+    rc = check_reserved_null(w->aux_stream, "eagcn_layer_route", "eagcn_layer_bufs.aux_stream");
+    if (rc) return rc;
     const LayerRoute r = plan_layer(b, p, w, layer_dims(b, p), PlanAsk{has_dx != 0, mol_grad != 0, input_only != 0, has_drain_out != 0});
     const int32_t v[16] = {(int32_t)r.fwd_prod, r.fwd_split_x, (int32_t)r.fwd_agg, (int32_t)r.bwd_agg, (int32_t)r.bn2, r.rows_first, r.rows_late, r.store_dh, (int32_t)r.edge,
                            r.edge_atomic, (int32_t)r.bwd_prod, r.bwd_split_x, r.defer_drain,
-                           layer_reads_planes_only(b, p, w->aux_stream != nullptr), 0, 0};
+                           layer_reads_planes_only(b, p), 0, 0};
     memcpy(out, v, sizeof(v));
     return EAGCN_OK;
 }
@@ -1196,7 +1184,8 @@ static int clear_handoff_flags(const eagcn_layer_bufs* w, void* stream) {
 extern "C" int eagcn_layer_forward(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w,
                                    void* stream) {
     EAGCN_CHECK_GEMM3("eagcn_layer_forward");
-    const int rc = clear_handoff_flags(w, stream);
+    int rc = check_reserved_null(w ? w->aux_stream : nullptr, "eagcn_layer_forward", "eagcn_layer_bufs.aux_stream");
+    if (!rc) rc = clear_handoff_flags(w, stream);
     return rc ? rc : layer_forward_impl(b, p, w, stream, false);
 }
 
@@ -1315,8 +1304,8 @@ int eagcn::layer_forward_impl(const eagcn_batch* b, const eagcn_layer_params* p,
 }
 
 // both directions of layer p would take their input x from its bf16 plane images alone: the route of a call that brings them
-bool eagcn::layer_reads_planes_only(const eagcn_batch* b, const eagcn_layer_params* p, bool aux_stream) {
-    if (!sw_planes_only() || aux_stream || !b || !p || b->T <= 0) return false;
+bool eagcn::layer_reads_planes_only(const eagcn_batch* b, const eagcn_layer_params* p) {
+    if (!sw_planes_only() || !b || !p || b->T <= 0) return false;
     // (bx3_ok looks at alignment, strides and extents: the addresses stand for the 256-byte aligned pieces the executors carve)
     void* const some = reinterpret_cast<void*>(static_cast<uintptr_t>(4096));
     eagcn_layer_bufs w;
@@ -1327,7 +1316,7 @@ bool eagcn::layer_reads_planes_only(const eagcn_batch* b, const eagcn_layer_para
 }
 
 // EAGCN_TOP_BN_SUMS=0 in the environment / eagcn_set_top_bn_sums(0): the top layer's BatchNorm backward keeps its reduction pass
-static int g_top_bn_sums = env_is("EAGCN_TOP_BN_SUMS", '0') ? 0 : env_is("EAGCN_TOP_BN_SUMS", '2') ? 2 : 1;
+static int g_top_bn_sums = !env_flag("EAGCN_TOP_BN_SUMS", true) ? 0 : env_int("EAGCN_TOP_BN_SUMS", 1) == 2 ? 2 : 1;
 bool eagcn::top_bn_sums_enabled() { return g_top_bn_sums != 0; }
 bool eagcn::top_bn_gather_enabled() { return g_top_bn_sums == 1; }
 extern "C" int eagcn_set_top_bn_sums(int on) {
@@ -1336,7 +1325,7 @@ extern "C" int eagcn_set_top_bn_sums(int on) {
     return old;
 }
 // EAGCN_HIDDEN_BN_SUMS=0 in the environment / eagcn_set_hidden_bn_sums(0): the hidden layers' BatchNorm backward keeps its reduction pass
-static int g_hidden_bn_sums = env_is("EAGCN_HIDDEN_BN_SUMS", '0') ? 0 : 1;
+static int g_hidden_bn_sums = env_flag("EAGCN_HIDDEN_BN_SUMS", true) ? 1 : 0;
 static long g_hidden_bn_taken = 0;
 /* layer backward calls (captured ones count when they are captured) that took dH and its sums from the layer above, since the last reset */
 extern "C" long eagcn_hidden_bn_sums_taken(int reset) {
@@ -1349,8 +1338,8 @@ extern "C" int eagcn_set_hidden_bn_sums(int on) {
     g_hidden_bn_sums = on ? 1 : 0;
     return old;
 }
-bool eagcn::layer_hidden_sums_route(const eagcn_batch* b, const eagcn_layer_params* up, const eagcn_layer_params* low, bool aux_stream, BxBnEpi* ep) {
-    if (!g_hidden_bn_sums || aux_stream || !b || !up || !low || b->T <= 0 || low->structure != EAGCN_STRUCT_CONCATE || !low->training) return false;
+bool eagcn::layer_hidden_sums_route(const eagcn_batch* b, const eagcn_layer_params* up, const eagcn_layer_params* low, BxBnEpi* ep) {
+    if (!g_hidden_bn_sums || !b || !up || !low || b->T <= 0 || low->structure != EAGCN_STRUCT_CONCATE || !low->training) return false;
     void* const some = reinterpret_cast<void*>(static_cast<uintptr_t>(4096));
     eagcn_layer_bufs w;
     memset(&w, 0, sizeof(w));
@@ -1370,13 +1359,12 @@ bool eagcn::layer_hidden_sums_route(const eagcn_batch* b, const eagcn_layer_para
 }
 // the backward of top layer p, given a per-molecule upstream gradient, would store dH in its reduction pass and leave the second pass
 // to lagg.hip: the one route whose reduction pass the read-out's sums replace (asked by the model engine before it forms them)
-bool eagcn::layer_top_sums_route(const eagcn_batch* b, const eagcn_layer_params* p, bool aux_stream) {
+bool eagcn::layer_top_sums_route(const eagcn_batch* b, const eagcn_layer_params* p) {
     if (!b || !p || b->T <= 0 || p->structure != EAGCN_STRUCT_CONCATE || !p->training) return false;
     void* const some = reinterpret_cast<void*>(static_cast<uintptr_t>(4096));
     eagcn_layer_bufs w;
     memset(&w, 0, sizeof(w));
     w.x_planes = static_cast<const uint16_t*>(some); w.x = static_cast<const float*>(some); w.P = static_cast<float*>(some); w.scratch = some;
-    w.aux_stream = aux_stream ? some : nullptr;
     const LayerRoute r = plan_layer(b, p, &w, layer_dims(b, p), PlanAsk{true, true, false, false, true});
     return r.bn2 == BN2_STAGED_FROM_READOUT && r.bwd_agg == AGG_LAGG && r.edge == EDGE_WITH_LAGG;
 }
@@ -1404,7 +1392,8 @@ extern "C" int eagcn_layer_backward(const eagcn_batch* b, const eagcn_layer_para
                                     const float* dxout, const float* dpad_row, float* dx,
                                     const eagcn_layer_grads* g, void* stream) {
     EAGCN_CHECK_GEMM3("eagcn_layer_backward");
-    const int rc = clear_handoff_flags(w, stream);
+    int rc = check_reserved_null(w ? w->aux_stream : nullptr, "eagcn_layer_backward", "eagcn_layer_bufs.aux_stream");
+    if (!rc) rc = clear_handoff_flags(w, stream);
     return rc ? rc : layer_backward_impl(b, p, w, dxout, dpad_row, dx, g, stream);
 }
 
@@ -1412,10 +1401,9 @@ namespace {
 // one backward call: its arguments, carving and route, and what the products leave for unpack_grads
 struct LayerBwd {
     const eagcn_batch* b; const eagcn_layer_params* p; const eagcn_layer_bufs* w;
-    const float* dxout; const float* dpad_row; float* dx; LayerBwdOpts o;
+    const float* dxout; const float* dpad_row; LayerBwdOpts o;
     LayerDims d; LayerScratch sc; LayerRoute r; ParamPtrs pp; GradPtrs gp; ColMapD in;
-    hipStream_t s, side;         // side: work that is off the dX critical path (edge gradients, dW product, gradient unpacking);
-    bool forked;                 // with no auxiliary stream everything stays in order on s
+    hipStream_t s;
     bool wt, dg; DropArgs drop; double gemm_work;
     int nsplit = 0, xk_G = 0;
     bool bx_slabs = false;       // dWcat holds the k-chunk slabs of the plane GEMM (all of them written)
@@ -1531,7 +1519,6 @@ static int bwd_batchnorm(LayerBwd& c) {
 static int bwd_aggregate(LayerBwd& c) {
     const eagcn_batch* b = c.b; const eagcn_layer_bufs* w = c.w; const LayerDims& d = c.d; const LayerScratch& sc = c.sc;
     const LayerRoute& r = c.r; hipStream_t s = c.s;
-    int rc;
     AggArgs a;
     a.bt = *b; a.vc = d.vc; a.src = sc.dY; a.lds = d.fp; a.dst = sc.dP; a.ldd = d.fp;
     a.sig = sc.pk.sig; a.rsig = sc.pk.rsig; a.rscale = w->rscale; a.stats = nullptr; a.nchunk = 1;
@@ -1555,11 +1542,7 @@ static int bwd_aggregate(LayerBwd& c) {
     case EDGE_NONE:              // input-only (agg.hip: molecules of more than 256 atoms, code books)
         return r.bwd_agg == AGG_LAGG ? launch_lagg_bwd(a, e, s, false) : launch_agg(a, true, s);
     case EDGE_WITH_LAGG: return launch_lagg_bwd(a, e, s);       // both from the same LDS gathers
-    case EDGE_COLAUNCH: return launch_agg_edge(a, e, s);        // one grid for both
-    default:
-        if (c.forked) { rc = stream_after(c.side, s); if (rc) return rc; }      // dY' is ready
-        rc = launch_edge_grad(e, c.side);
-        return rc ? rc : launch_agg(a, true, s);
+    default: return launch_agg_edge(a, e, s);                   // EDGE_COLAUNCH: one grid for both
     }
 }
 
@@ -1614,9 +1597,7 @@ static int bwd_products(LayerBwd& c, const LayerOperands& o) {
         c.nsplit = 0;                                 // no partial slabs: unpack_grads only reduces the edge partials
         return rc;
     case BWD_TILED_PAIR: return launch_gemm_pair(gq.gx, gq.gw, s);              // dX and dW share one grid
-    default:
-        rc = launch_gemm(gq.gw, c.side);
-        return (rc || !c.dx) ? rc : launch_gemm(gq.gx, s);
+    default: return launch_gemm(gq.gw, s);           // BWD_TILED_SEPARATE: dW alone (no dX was asked for)
     }
 }
 
@@ -1627,7 +1608,7 @@ static int bwd_unpack(LayerBwd& c) {
         // a batch without a single bond has no packed row: no product ran, the weight gradients are exactly zero (the edge
         // partials below are summed over zero workgroups; the BatchNorm gradients came from the row-less reduction)
         for (int k = 0; k < p->K; ++k)
-            { int rcz = zero_fill(c.gp.dW[k], (size_t)d.fin * p->width[k] * sizeof(float), c.side); if (rcz) return rcz; }
+            { int rcz = zero_fill(c.gp.dW[k], (size_t)d.fin * p->width[k] * sizeof(float), c.s); if (rcz) return rcz; }
     }
     if (c.r.defer_drain) {
         EdgeDrain* out = c.o.drain_out;
@@ -1640,8 +1621,8 @@ static int bwd_unpack(LayerBwd& c) {
     const int wblocks = c.nsplit > 0 ? cdiv((int)d.wslab, 256) : 0;     // (one thread per element: four lanes per four elements, unpack_grads)
     const bool shared = b->T > 0 && c.r.edge_atomic;                    // shared accumulators: zeroed again by the threads that read them
     const int nedge = b->T > 0 ? (shared ? -EDGE_COPIES : edge_grid_x(b)) : 0;
-    ProfScope psu(PROF_PACK, c.side);
-    unpack_grads_kernel<<<wblocks + cdiv(p->K * EDGE_SLAB, 16), 256, 0, c.side>>>(c.gp, c.pp, d.vc, c.in, d.ld_in, d.fp, sc.dWcat,
+    ProfScope psu(PROF_PACK, c.s);
+    unpack_grads_kernel<<<wblocks + cdiv(p->K * EDGE_SLAB, 16), 256, 0, c.s>>>(c.gp, c.pp, d.vc, c.in, d.ld_in, d.fp, sc.dWcat,
                                                                                   c.bx_slabs ? -c.nsplit : c.nsplit, d.wslab,
                                                                                   shared ? sc.eacc : sc.datt, nedge, sc.pk.rsig,
                                                                                   wblocks, b->meta, c.xk_G, shared ? 1 : 0, c.bx_per, c.bx_wide);
@@ -1664,7 +1645,7 @@ int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p
             EAGCN_CHECK_ARG(g->dW[k] && g->dbias[k] && g->dgamma[k] && g->dbeta[k] && g->datt_w[k] && g->dself_r[k],
                             "eagcn_layer_backward: view %d has a null gradient buffer", k);
     LayerBwd c;
-    c.b = b; c.p = p; c.w = w; c.dxout = dxout; c.dpad_row = dpad_row; c.dx = dx; c.o = o;
+    c.b = b; c.p = p; c.w = w; c.dxout = dxout; c.dpad_row = dpad_row; c.o = o;
     c.d = layer_dims(b, p);
     const LayerDims& d = c.d;
     rc = carve_checked(b, w, d, true, &c.sc, "eagcn_layer_backward");      // (packed: re-laid by the forward call and kept)
@@ -1672,8 +1653,6 @@ int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p
     if (o.input_only)
         EAGCN_CHECK_ARG(d.wslab >= (size_t)3 * d.fp + EAGCN_MAX_VIEWS, "eagcn_layer_backward: no room for the discarded BatchNorm gradients");
     c.s = (hipStream_t)stream;
-    c.side = w->aux_stream ? (hipStream_t)w->aux_stream : c.s;
-    c.forked = c.side != c.s;
     c.wt = p->structure == EAGCN_STRUCT_WEIGHTED;
     c.dg = o.rg && o.rg->dg;
     c.pp = param_ptrs(b, p);
@@ -1689,7 +1668,7 @@ int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p
     bool gather = o.top_sums && o.top_dge && (reinterpret_cast<uintptr_t>(o.top_dge) & 15) == 0 && o.rg && (o.rg->F & 3) == 0;
     for (int k = 0; k < p->K; ++k) gather = gather && (p->width[k] & 3) == 0;
     EAGCN_CHECK_ARG(!o.dh_sums || (o.dh_nslab >= hidden_bn_slabs(b->T) && dxout && !c.dg && !o.input_only && !o.drain_in && !o.zero_after &&
-                                   !dpad_row && p->training && !w->stats_hook && !w->aux_stream && !o.top_sums),
+                                   !dpad_row && p->training && !w->stats_hook && !o.top_sums),
                     "eagcn_layer_backward: dH and its column sums from the layer above belong to a hidden layer in training mode with a local BatchNorm");
     c.r = plan_layer(b, p, w, d, PlanAsk{dx != nullptr, c.dg, o.input_only, o.drain_out != nullptr, o.top_sums != nullptr, gather, o.dh_sums != nullptr});
     if (o.below_done) *o.below_done = false;
@@ -1718,16 +1697,11 @@ int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p
         }
         rc = bwd_aggregate(c);
         if (rc) return rc;
-        if (c.forked && !o.input_only) { rc = stream_after(c.side, c.s); if (rc) return rc; }          // dP is ready
         rc = bwd_products(c, layer_operands(w, c.sc, dx));
         if (rc) return rc;
     }
     if (o.input_only) return EAGCN_OK;                 // (no parameter gradient is formed)
-    rc = bwd_unpack(c);
-    if (rc) return rc;
-    // join: the caller reuses the scratch block (dY', dP, partial slabs) for the next layer
-    if (c.forked && !c.r.defer_drain) { rc = stream_after(c.s, c.side); if (rc) return rc; }
-    return EAGCN_OK;
+    return bwd_unpack(c);
 }
 
 extern "C" int eagcn_attention_dense(const eagcn_batch* b, const eagcn_layer_params* p, float* out, void* stream) {

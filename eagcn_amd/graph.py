@@ -176,12 +176,7 @@ class GraphRunner:
         self.n_in = N                  # padded size of the current batch's tensors (EAGCN(n_bucket=...): may be < N)
         self.generation = 0
         self.size_static = [torch.ones(B, dtype=torch.int64, device=device) for _ in range(2)]
-        self.aux = None
         self.dp_group = None
-        # optional fork of off-critical-path backward work onto a second stream (graph branches).
-        # Measured on MI355X at the Tox21 shape: replay got SLOWER (0.85 vs 0.77 ms/step), so off by default.
-        if os.environ.get('EAGCN_AUX_STREAM', '0') == '1':
-            self.aux = torch.cuda.Stream(device=self.device)
         self.fwd_sig = torch.zeros(1, dtype=torch.int32, device=device)     # bumped by every executed forward (eagcn_model.fwd_signal)
         # the next batch's index build held back until this step's forward has passed its read-out (module comment at _SIDE_PLACED)
         self.side_placed = _SIDE_PLACED == '1' or (_SIDE_PLACED == 'auto' and B * N <= _SIDE_PLACED_MAX_ROWS)
@@ -282,8 +277,6 @@ class GraphRunner:
             m.start_signal = self.start_word.data_ptr()
         if self.side_placed:
             m.fwd_signal = self.fwd_sig.data_ptr()
-        if self.aux is not None:
-            m.aux_stream = self.aux.cuda_stream
         return m
 
     def stale(self):

@@ -191,9 +191,9 @@ typedef struct eagcn_layer_bufs {
     float* pad_row;                         /* [ld_out] value of every non-stored row of xout   */
     void* scratch;
     size_t scratch_bytes;
-    void* aux_stream;                       /* optional second hipStream_t: backward runs the edge  */
-                                            /* gradients and the dW product there, concurrently     */
-                                            /* with the dX chain (fork/join by events; capturable)  */
+    void* aux_stream;                       /* reserved, must be NULL (a value: EAGCN_ERR_ARG). The */
+                                            /* backward runs on the one stream of the call; the     */
+                                            /* field keeps the struct's layout                      */
     void* packed;                           /* optional, eagcn_layer_packed_bytes(): forward keeps  */
     size_t packed_bytes;                    /* the re-laid parameters here and backward reuses them */
     eagcn_allreduce_fn stats_hook;          /* sync-BatchNorm: cross-rank sum of the BatchNorm partial sums (NULL: local-BN) */
@@ -250,10 +250,11 @@ size_t eagcn_layer_bwd_scratch_bytes(const eagcn_batch* b, const eagcn_layer_par
  *           upstream gradient and the row mask (eval-mode input-only Concate)
  *   out[5]  the per-molecule gradient is written as rows before the reduction    out[6] ... after it (never both)
  *   out[7]  the reduction stores dH
- *   out[8]  edge gradients      0 none | 1 inside the LDS-staged aggregation | 2 one grid with the aggregation | 3 own launch
+ *   out[8]  edge gradients      0 none | 1 inside the LDS-staged aggregation | 2 one grid with the aggregation (3, an own launch,
+ *           is no longer produced)
  *   out[9]  ... leave through the shared fp64 accumulators
  *   out[10] backward products   0 none | planes: 1 dX with dW | 2 dW alone | 3 dX alone | balanced pair: 4 XCD-local slabs |
- *           5 dW scattered in place | tiled: 6 pair | 7 separate launches | 8 dX alone | 9 refused (as out[0])
+ *           5 dW scattered in place | tiled: 6 pair | 7 dW alone (no dX asked) | 8 dX alone | 9 refused (as out[0])
  *   out[12] the edge-gradient reduction is left to the next layer's first backward kernel
  *   out[13] a layer handed plane images of x alone would cope in both directions (what the model engine asks before it drops the
  *           fp32 matrix: out[0] == 1 and out[10] == 1 of a call with has_dx that brings x_planes)
@@ -386,7 +387,7 @@ typedef struct eagcn_model {
     uint64_t head_seed;                     /* dropout stream of the head (models.py:116)              */
     const uint64_t* head_seed_dev;          /* device-resident alternative (see eagcn_layer_params)    */
     int32_t input_packed;                   /* 1: saved already holds the packed input (eagcn_model_pack_input) */
-    void* aux_stream;                       /* optional second stream for off-critical-path backward work */
+    void* aux_stream;                       /* reserved, must be NULL (a value: EAGCN_ERR_ARG); keeps the layout */
     eagcn_layer_params layer[4];            /* layer[l].in must equal the output layout of layer l-1   */
     eagcn_head_params head;
     eagcn_allreduce_fn stats_hook;          /* sync-BatchNorm of EVERY BatchNorm of the model (the per-view ones of the layers and

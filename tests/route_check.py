@@ -1,7 +1,8 @@
 """Run by test_host_cpu.py in a subprocess per environment (the library reads its switches once): eagcn_layer_route over a cross
 product of batches, layers and calls against the routes WRITTEN OUT here from the policy's description (DESIGN.md "the route of
-a layer call"), never derived from the library; the invariants of a route; and, with no switch set, the pinned sizes of the
-three carvings.  No GPU: every address is a made-up multiple of 4096 and nothing is dereferenced."""
+a layer call"), never derived from the library; the invariants of a route; that a call which sets the reserved field
+eagcn_layer_bufs.aux_stream is refused; and, with no switch set, the pinned sizes of the three carvings.  No GPU: every address
+is a made-up multiple of 4096 and nothing is dereferenced."""
 import ctypes as C
 import importlib.util
 import itertools
@@ -19,7 +20,8 @@ CONCATE, WEIGHTED = L.STRUCT_CONCATE, L.STRUCT_WEIGHTED
  PLANES_ONLY) = range(14)
 FWD_PLANES, FWD_BALANCED, FWD_TILED, FWD_REFUSED = 1, 2, 3, 4
 ELEMENTWISE, REDUCE_APPLY, STAGED_DH, STAGED_UPSTREAM, STAGED_ROWMASK = 1, 2, 3, 4, 5
-WITH_LAGG, COLAUNCH, SEPARATE = 1, 2, 3
+WITH_LAGG, COLAUNCH = 1, 2
+ERR_ARG = -1                                                     # EAGCN_ERR_ARG
 PLANES_PAIR, PLANES_DW, PLANES_DX, G3_XK, G3_SCATTER, TILED_PAIR, TILED_SEPARATE, TILED_DX, BWD_REFUSED = range(1, 10)
 
 _next = [1 << 24]
@@ -79,7 +81,7 @@ def make_bufs(x, x_planes, aux):
     return w
 
 
-def expected(structure, batch, layer, mol_grad, training, input_only, aux, has_dx, env):
+def expected(structure, batch, layer, mol_grad, training, input_only, has_dx, env):
     """The route, from the description of the policy.  None: not pinned for this call."""
     B, N, T, lists, codebook = BATCHES[batch]
     segs, _, x, x_planes, _, drain_out = LAYERS[layer]
@@ -116,23 +118,23 @@ def expected(structure, batch, layer, mol_grad, training, input_only, aux, has_d
         e[BN2] = REDUCE_APPLY
     else:
         e[BN2] = STAGED_DH if lagg else ELEMENTWISE
-    planes = np_ and not aux
+    planes = np_
     e[BWD_SPLIT] = int(planes and not x_planes and not input_only)
-    e[PLANES_ONLY] = int(np_ and not aux)
+    e[PLANES_ONLY] = int(np_)
     if input_only:
         e[BWD_PROD] = PLANES_DX if planes else TILED_DX
         return e
     if not planes and not x:
         e[BWD_PROD] = BWD_REFUSED
         return e
-    e[EDGE] = WITH_LAGG if lagg else SEPARATE if aux else COLAUNCH
+    e[EDGE] = WITH_LAGG if lagg else COLAUNCH
     if planes:
         e[BWD_PROD] = PLANES_PAIR if has_dx else PLANES_DW
-    elif gemm3 and has_dx and not aux:
+    elif gemm3 and has_dx:
         e[BWD_PROD] = G3_SCATTER
     else:
-        e[BWD_PROD] = TILED_PAIR if has_dx and not aux else TILED_SEPARATE
-    e[DEFER] = int(drain_out and not codebook and e[BWD_PROD] == G3_SCATTER and not aux)
+        e[BWD_PROD] = TILED_PAIR if has_dx else TILED_SEPARATE
+    e[DEFER] = int(drain_out and not codebook and e[BWD_PROD] == G3_SCATTER)
     return e
 
 
@@ -179,7 +181,7 @@ def main():
         for key, want in SIZES.items():
             got = sizes(lib, *key)
             assert got == want, (key, got, want)
-    n = 0
+    n = refused = 0
     for structure, batch, layer in itertools.product((CONCATE, WEIGHTED), BATCHES, LAYERS):
         segs, width, x, x_planes, has_dx, drain_out = LAYERS[layer]
         c = make_batch(*BATCHES[batch])
@@ -191,14 +193,18 @@ def main():
             rc = lib.eagcn_layer_route(C.byref(c), C.byref(p), C.byref(w), dx, mol_grad, input_only, drain_out, C.byref(out))
             what = dict(structure=structure, batch=batch, layer=layer, mol_grad=mol_grad, training=training, input_only=input_only,
                         aux=aux, env=env)
+            if aux:                                             # the reserved field is set: refused, by name
+                assert rc == ERR_ARG and b'aux_stream' in lib.eagcn_last_error(), (what, rc, lib.eagcn_last_error())
+                refused += 1
+                continue
             assert rc == 0, (what, lib.eagcn_last_error())
             r = list(out)
-            want = expected(structure, batch, layer, mol_grad, training, input_only, aux, dx, env)
+            want = expected(structure, batch, layer, mol_grad, training, input_only, dx, env)
             diff = {i: (r[i], want[i]) for i in range(16) if want[i] is not None and r[i] != want[i]}
             assert not diff, (what, 'out[i]: (got, want)', diff)
             check_invariants(r, training, input_only, x_planes, dx, what)
             n += 1
-    print('routes checked:', n)
+    print('routes checked: %d, refusals checked: %d' % (n, refused))
 
 
 if __name__ == '__main__':

@@ -360,8 +360,9 @@ assert got == [1, 1, 1, 1, 1, 0, 1, 1, 0], got
                          ids=lambda s: ','.join('%s=%s' % kv for kv in s.items()) or 'default')
 def test_layer_routes_by_batch_layer_and_call(switches):
     """eagcn_layer_route (csrc/layer.hip plan_layer: which kernels a layer call runs, decided once) against the routes written out
-    in tests/route_check.py: structure x batch shape x layer kind x per-molecule gradient x training x input-only x auxiliary
-    stream, the invariants of every route and -- with no switch set -- the pinned byte counts of the three carvings.  The plain
+    in tests/route_check.py: structure x batch shape x layer kind x per-molecule gradient x training x input-only, the invariants
+    of every route, the refusal (EAGCN_ERR_ARG) of each of those calls once it sets the reserved field eagcn_layer_bufs.aux_stream
+    and -- with no switch set -- the pinned byte counts of the three carvings.  The plain
     fp32 mode (EAGCN_GEMM_X6=0) is what reaches the balanced kernels EAGCN_NO_GEMM3 turns off.  In a subprocess: the library
     reads its switches once."""
     import subprocess
@@ -369,7 +370,7 @@ def test_layer_routes_by_batch_layer_and_call(switches):
     env = {k: v for k, v in os.environ.items() if not k.startswith('EAGCN_')}
     env.update(switches)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'route_check.py')], capture_output=True, text=True, cwd=str(ROOT), env=env)
-    assert r.returncode == 0 and 'routes checked: 672' in r.stdout, r.stdout + r.stderr
+    assert r.returncode == 0 and 'routes checked: 336, refusals checked: 336' in r.stdout, r.stdout + r.stderr
 
 
 def test_bond_list_buffers_are_laid_out_without_overlap():
@@ -499,3 +500,27 @@ def test_gradient_descriptors_point_into_the_flat_buffer(cls):
     for j, (name, (mn, pn)) in enumerate(zip(ops.HEAD_GRADS, ops.HEAD_PARAMS)):
         assert getattr(hg, name) == flat.data_ptr() + 4 * plan.offsets[plan.head_start + j] == slot(getattr(getattr(model, mn), pn))
     assert ops.HEAD_GRADS == ('d_den1_w', 'd_den2_w', 'd_den3_w', 'd_gbn_w', 'd_gbn_b', 'd_bn1_w', 'd_bn1_b', 'd_bn2_w', 'd_bn2_b')
+
+
+def test_environment_switches_read_are_the_ones_documented():
+    """Documentation drift only (no compiled code is inspected): the EAGCN_* names the library (csrc, through env_int / env_flag /
+    getenv), the Python package and bench.py (through os.environ) read from the environment are exactly the names in the first
+    column of the table of INTEGRATION.md section 5 -- the C macros of include/eagcn_hip.h (EAGCN_STRUCT_*, ...) set aside."""
+    import glob
+    files = glob.glob(os.path.join(ROOT, 'eagcn_amd', 'csrc', '*')) + glob.glob(os.path.join(ROOT, 'eagcn_amd', '*.py')) + \
+        [os.path.join(ROOT, 'bench.py')]
+    read_call = re.compile(r'(?:\benv_int|\benv_flag|\bgetenv|\benviron(?:\.\w+)?)\s*[(\[]\s*[\'"](EAGCN_[A-Z0-9_]+)[\'"]')
+    read = set()
+    for f in files:
+        read |= set(read_call.findall(open(f).read()))
+    assert len(read) >= 40, sorted(read)                     # (the pattern still finds the reads)
+    macros = set(re.findall(r'#define\s+(EAGCN_[A-Z0-9_]+)', open(os.path.join(ROOT, 'include', 'eagcn_hip.h')).read()))
+    doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
+    section = doc[doc.index('## 5. Environment switches'):]
+    section = section[:section.index('\n## ', 1)] if '\n## ' in section[1:] else section
+    documented = set()
+    for line in section.split('\n'):
+        if line.startswith('| `EAGCN_'):
+            documented |= set(re.findall(r'EAGCN_[A-Z0-9_]+', line.split('|')[1]))
+    documented -= macros
+    assert read == documented, {'read but not in the table': sorted(read - documented), 'in the table but not read': sorted(documented - read)}

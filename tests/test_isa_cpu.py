@@ -1,7 +1,7 @@
 """The ISA the BASELINE configs actually run carries no scratch traffic in its hot loops (spills had come back
-into the MFMA loops of agg_edge<9,false>, agg_wave<9,*> and bx3_kernel<3,0> unnoticed).  hipcc cross-compiles gfx950 here, no GPU
+into the MFMA loops of agg_edge<9,false>, agg_wave<9,*> and bx3_kernel<3> unnoticed).  hipcc cross-compiles gfx950 here, no GPU
 needed: every dispatched instantiation of the aggregation kernels must have private_segment_fixed_size == 0, and no basic block of
-the plane GEMMs that issues matrix instructions may touch scratch (bx3_kernel<3,0> keeps a few one-time spills of its loader
+the plane GEMMs that issues matrix instructions may touch scratch (bx3_kernel<3> keeps a few one-time spills of its loader
 prologue: 256 registers are shared by two roles)."""
 import os
 import re
@@ -92,13 +92,15 @@ def _mfma_blocks_with_scratch(text, kernel):
 
 
 def test_plane_gemm_loops_do_not_touch_scratch(isa):
-    for src, kernel in (('gemm_bx3', 'bx3_kernelILi3ELi0E'), ('gemm_bx3', 'bx3_kernelILi1ELi0E'), ('gemm_bx3w', 'bx3w_kernelILi3ELi4ELi0E'),
-                        ('gemm_bx3w', 'bx3w_kernelILi1ELi4ELi0E')):
+    for src, kernel in (('gemm_bx3', 'bx3_kernelILi3EE'), ('gemm_bx3', 'bx3_kernelILi1EE'), ('gemm_bx3w', 'bx3w_kernelILi3EE'),
+                        ('gemm_bx3w', 'bx3w_kernelILi1EE')):
         assert _mfma_blocks_with_scratch(isa[src], kernel) == [], (kernel, 'scratch access inside a block that issues MFMAs')
     ks = _kernels(isa['gemm_bx3w'])
-    for name, (scratch, vgpr) in ks.items():
-        if 'bx3w_kernelILi3ELi4ELi0E' in name or 'bx3w_kernelILi1ELi4ELi0E' in name:
-            assert scratch == 0 and vgpr <= 256, (name, scratch, vgpr)            # two compute waves per SIMD
+    wide = [name for name in ks if 'bx3w_kernelILi3EE' in name or 'bx3w_kernelILi1EE' in name]
+    assert len(wide) == 2, sorted(ks)
+    for name in wide:
+        scratch, vgpr = ks[name]
+        assert scratch == 0 and vgpr <= 256, (name, scratch, vgpr)                # two compute waves per SIMD
 
 
 def test_head_kernels_have_no_scratch(isa):
