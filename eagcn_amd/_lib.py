@@ -237,6 +237,9 @@ SIGNATURES = {
     'eagcn_set_top_bn_sums': (C.c_int, [C.c_int]),
     'eagcn_set_hidden_bn_sums': (C.c_int, [C.c_int]),
     'eagcn_hidden_bn_sums_taken': (C.c_long, [C.c_int]),
+    'eagcn_set_first_layer_fused': (C.c_int, [C.c_int]),
+    'eagcn_first_layer_fused_taken': (C.c_long, [C.c_int]),
+    'eagcn_first_layer_fused_last': (None, [C.POINTER(C.c_int32)]),
     'eagcn_bx3_pair_used_splits': (C.c_int, [C.c_int] * 7),
     'eagcn_bx3_plane_elems': (C.c_size_t, [C.c_int, C.c_int]),
     'eagcn_bx3_split': (C.c_int, [_fp, C.c_int, C.c_int, _fp, C.c_size_t, C.c_int, C.c_int, _fp]),

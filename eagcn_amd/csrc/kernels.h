@@ -35,6 +35,10 @@ struct AggArgs {
     // is re-formed in the staging as well -- neither dH nor dY' of the layer (T x K F floats each) ever exists in memory
     const float* w_aw = nullptr;                 // [Fp] the view weight per packed column (colp row CP_AVEW)
     int w_drop = 0; uint32_t w_thr = 0; float w_inv_keep = 1.0f; uint64_t w_seed = 0; const uint64_t* w_seed_dev = nullptr;
+    // transposed with the edge gradients, lagg_dw.hip (a first layer whose input gradient nobody asks for): dP is not stored; the
+    // weight gradient fx^T . dP leaves as one slab per workgroup row, dw [dw_ny][fx_ld][Fp] (fx: the layer's input [T][fx_ld],
+    // fx_ld <= 32); the launch's y extent is dw_ny, every slab is written whatever the block count
+    const float* fx = nullptr; int fx_ld = 0; float* dw = nullptr; size_t dw_slab = 0; int dw_ny = 0;
 };
 // dropout of an activation as the kernels draw it: keep where hash(seed, element) >= thr, scaled by inv_keep (seed_dev: the seed
 // read on the device instead).  The ONE place threshold and scale are derived from the probability
@@ -66,6 +70,9 @@ int launch_lagg_bwd(AggArgs a, const EdgeArgs& e, hipStream_t s, bool edge = tru
 int launch_lagg_bwd_input(const AggArgs& a, const EdgeArgs& e, dim3 grid, hipStream_t s);
 // lagg_top.hip: the row-mask staging WITH the edge gradients (Concate top layer whose dH is never stored), same grid
 int launch_lagg_bwd_top(const AggArgs& a, const EdgeArgs& e, dim3 grid, hipStream_t s);
+// lagg_dw.hip: the plain transposed kernel with the weight gradient in its epilogue (AggArgs.dw), same grid with y = AggArgs.dw_ny
+int launch_lagg_bwd_dw(const AggArgs& a, const EdgeArgs& e, dim3 grid, hipStream_t s);
+int lagg_bwd_grid_y(const eagcn_batch* b, const ViewCols& vc);    // y extent launch_lagg_bwd gives its grid for this batch
 
 struct EdgeArgs {
     eagcn_batch bt;

@@ -155,6 +155,12 @@ static int lagg_grid(const AggArgs& a, dim3* grid, int* nchunk, int* cpw, bool t
     return EAGCN_OK;
 }
 
+int lagg_bwd_grid_y(const eagcn_batch* b, const ViewCols& vc) {
+    int chunks, gy;
+    lagg_extent(*b, vc, &chunks, &gy);
+    return gy;
+}
+
 int launch_lagg_fwd(AggArgs a, hipStream_t s) {
     if (a.bt.B == 0 || a.bt.T == 0) return EAGCN_OK;
     dim3 grid;
@@ -183,6 +189,10 @@ int launch_lagg_bwd(AggArgs a, const EdgeArgs& e, hipStream_t s, bool edge) {
         if (rc) return rc;
     } else if (a.w_rowm) {
         rc = launch_lagg_bwd_top(a, e, grid, s);                      // Concate top layer without a stored dH: lagg_top.hip
+        if (rc) return rc;
+    } else if (a.dw) {
+        grid.y = (unsigned)std::max(1, std::min((int)grid.y, a.dw_ny));       // (never more workgroup rows than slabs: the kernel loops)
+        rc = launch_lagg_bwd_dw(a, e, grid, s);                       // weight gradient in the epilogue, no dP: lagg_dw.hip
         if (rc) return rc;
     } else if (a.w_aw) {
         // (one instantiation: with one chunk per workgroup the records of a block are simply built in front of its only chunk; the

@@ -1,6 +1,7 @@
 // The LDS-staged bond-list aggregation kernel (lagg.hip: the design notes, the policy and the launches of the edge-gradient forms;
 // lagg_in.hip: the launches of the input-only backward's forms, EDGE = false; lagg_top.hip: the row-mask staging with the edge
-// gradients).  One template, instantiated in those three translation units only.
+// gradients; lagg_dw.hip: the first layer's weight gradient in the epilogue).  One template, instantiated in those four translation
+// units only.
 #pragma once
 
 #include "common.h"
@@ -62,8 +63,15 @@ constexpr int LG_NOVF = 32;
 //   (c1 = c2 = 0); EDGE = true (lagg_top.hip): a top layer in training mode whose BatchNorm means came from the read-out's sums
 // GATHER (with CROWS and EDGE): a.src is that gradient per MOLECULE, [B][a.lds] at the EXACT column (AggArgs.w_gather): a row loads its
 //   molecule's four columns (the molecule of a row is in LDS since barrier R2; view widths are multiples of four there)
-template <bool TRANS, bool MULTI, bool WFUSE = false, bool EDGE = true, bool CROWS = false, bool GATHER = false>
+// DWF (transposed with the edge gradients, lagg_dw.hip; a layer of at most 32 input columns whose input gradient nobody asks for): dP is
+//   not stored.  Behind the row loop the block's dP takes the place of the staged dY' in `buf` and the workgroup forms its piece of the
+//   weight gradient, X_block^T . dP_block (a.fx_ld x 32), on the fp32 matrix cores: X straight from memory into the operand registers,
+//   dP from LDS, the four waves split the rows and are summed in wave order.  The piece goes into the slab of blockIdx.y
+//   (a.dw [gridDim.y][fx_ld][Fp]; further blocks of the workgroup are added to it, a workgroup without rows writes zeros):
+//   unpack_grads sums the slabs in slot order -- no float atomics anywhere
+template <bool TRANS, bool MULTI, bool WFUSE = false, bool EDGE = true, bool CROWS = false, bool GATHER = false, bool DWF = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void lagg_kernel(AggArgs a, EdgeArgs ed) {
+    static_assert(!DWF || (TRANS && EDGE && !WFUSE), "the weight-gradient epilogue belongs to the plain transposed kernel with the edge gradients");
     static_assert(TRANS || !WFUSE, "the upstream-gradient form belongs to the transposed kernel");
     static_assert(TRANS || EDGE, "the forward has no edge gradients to drop");
     static_assert(!CROWS || WFUSE, "the row-mask staging is a form of the upstream-gradient staging");
@@ -154,6 +162,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
     // A workgroup takes the blocks q, q + gridDim.y, ... (the grid's y extent is an estimate of the block count).  Measured and
     // dropped: a software pipeline over a workgroup's blocks (the next block's rows in flight into registers while this one is worked
     // on, a persistent grid of three workgroups per CU): 212 / 238 registers = two workgroups per CU instead of three, and slower.
+    // DWF: this lane's elements of the workgroup's piece of the weight gradient (chunk cc: element e = tid + 256 i of [32 input
+    // columns][32 columns]); first = the slab holds nothing of this workgroup yet: stored, else added (the same lane wrote it)
+    int nacc = 0;                                                     // DWF: blocks with rows this workgroup has taken (uniform)
+    auto dw_out = [&](int cc, int i, float t, bool first) __attribute__((always_inline)) {
+        const int e = tid + 256 * i, m = e >> 5, cv = cc * LG_CW + (e & 31);
+        if (m < a.fx_ld && cv < wk) {
+            float* dp = a.dw + (size_t)blockIdx.y * a.dw_slab + (size_t)m * a.vc.off[a.vc.K] + a.vc.off[k] + cv;
+            *dp = first ? t : *dp + t;
+        }
+    };
     for (int q = blockIdx.y; q < nblk; q += gridDim.y) {
         // the block: {first molecule, molecules, first packed row, rows} {first list entry, entries} -- one dependent load, then everything
         const int4 b0 = b0n, b1 = b1n;
@@ -555,6 +573,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
                 }
             }
         };
+        // DWF: the rows' dP stay in registers (a row's takes the place of its P row, which the edge gradients are done with) until no
+        // row gathers from `buf` any more; rows beyond the block's hold zeros
+        float4 ys[DWF ? LG_U : 1];
         bool any_slow = false;
         {
             // (forward: the NEXT row's record is read while this row's gathers are in flight; the transposed kernel has no registers to
@@ -570,7 +591,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
             const int nu = (rows + LG_G - 1) / LG_G;
 #pragma unroll
             for (int u = 0; u < LG_U; ++u) {
-                if (u >= nu) break;                                   // (uniform)
+                if (!DWF && u >= nu) break;                           // (uniform; DWF: every ys[u] is set, short blocks run on clamped rows)
                 const int rr = min(g + LG_G * u, rows - 1);
                 const bool valid = g + LG_G * u < rows;
                 if constexpr (!AHEAD) {
@@ -629,7 +650,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
                         if (l < 4 && hv2 != 0.0f && cv2) atomicAdd(&h_s[cv2], (double)hv2 * ((double)gv2 - (double)s_rd[sv2]));
                     }
                 }
-                if (fast) finish(rr, y);
+                if constexpr (DWF) ys[u] = fast ? y : make_float4(0.f, 0.f, 0.f, 0.f);
+                else { if (fast) finish(rr, y); }
             }
         }
         if (any_slow) {
@@ -692,7 +714,62 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
                         if (l == 0 && sj != 0.0f && !self_bond) dr_acc += (double)(sj * (gs - s_rd[rr]));
                     }
                 }
-                finish(rr, y);
+                if constexpr (DWF) {
+#pragma unroll
+                    for (int q8 = 0; q8 < LG_U; ++q8)                 // (constant register indices)
+                        if (q8 == u) ys[q8] = y;
+                } else finish(rr, y);
+            }
+        }
+        if constexpr (DWF) {
+            float* bf = reinterpret_cast<float*>(&buf[0][0]);
+            const int li = lane & 15, kq = lane >> 4;
+            __syncthreads();                                          // E1: no row gathers from the staged dY' any more
+#pragma unroll
+            for (int u = 0; u < LG_U; ++u) buf[g + LG_G * u][l] = ys[u];          // (all LAGG_RB rows: zeros beyond the block's)
+            // X^T: k-step ks of wave w is the rows 64 w + 4 ks + (lane >> 4), lane & 15 the input column of the 16 x 16 tile (columns
+            // beyond the layer's: a legal one -- those rows of the product are not stored); one batch of loads in front of the barrier
+            // (32-bit element offsets on the uniform base, formed HERE: hoisted out of the chunk loop they cost the several-chunk form 60 spilled registers)
+            float xa[16][2];
+            int rq = 64 * wave + kq;
+            asm volatile("" : "+v"(rq));
+            {
+                const uint32_t c0x = (uint32_t)min(li, a.fx_ld - 1), c1x = (uint32_t)min(16 + li, a.fx_ld - 1);
+#pragma unroll
+                for (int ks = 0; ks < 16; ++ks) {
+                    const uint32_t ro = (uint32_t)(R0 + min(rq + 4 * ks, rows - 1)) * (uint32_t)a.fx_ld;
+                    xa[ks][0] = a.fx[ro + c0x];
+                    xa[ks][1] = a.fx[ro + c1x];
+                }
+            }
+            __syncthreads();                                          // E2: the block's dP is in LDS
+            typedef float lg_f32x4 __attribute__((ext_vector_type(4)));
+            lg_f32x4 acc[2][2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = lg_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 16; ++ks) {
+                const float b0 = bf[(rq + 4 * ks) * LG_CW + li], b1 = bf[(rq + 4 * ks) * LG_CW + 16 + li];
+                acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[ks][0], b0, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[ks][0], b1, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[ks][1], b0, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[ks][1], b1, acc[1][1], 0, 0, 0);
+            }
+            __syncthreads();                                          // E3: every wave has read its rows of dP: the partials take their place
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int rr4 = 0; rr4 < 4; ++rr4)                 // (D layout: column = lane & 15, row = 4 (lane >> 4) + register)
+                        bf[wave * 1024 + (16 * i + 4 * kq + rr4) * LG_CW + 16 * j + li] = acc[i][j][rr4];
+            __syncthreads();                                          // E4
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int e = tid + 256 * i;
+                dw_out(cc, i, (bf[e] + bf[1024 + e]) + (bf[2048 + e] + bf[3072 + e]), nacc == 0);
             }
         }
         if constexpr (!TRANS) {
@@ -716,7 +793,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
             }
         }
         }                                                             // (chunks)
+        if constexpr (DWF) ++nacc;
     }                                                                 // (blocks)
+    if constexpr (DWF) {
+        if (nacc == 0) {                                              // (uniform) no block, or none with rows: the slab still has to be defined
+            for (int cc = cc_lo; cc < cc_hi; ++cc)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) dw_out(cc, i, 0.0f, true);
+        }
+    }
     if constexpr (TE) {
         if (dr_acc != 0.0) atomicAdd(&h_s[256], dr_acc);
         __syncthreads();

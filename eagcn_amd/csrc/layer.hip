@@ -646,7 +646,8 @@ __global__ __launch_bounds__(256) void unpack_grads_kernel(GradPtrs gp, ParamPtr
                                                             int ld_in, int fp, const float* __restrict__ dWcat,
                                                             int nsplit, size_t slab, double* __restrict__ datt,
                                                             int nedge, const float* __restrict__ rsig, int wblocks,
-                                                            const int32_t* __restrict__ meta, int xk_G, int edge_drain, int bx_per, int bx_wide) {
+                                                            const int32_t* __restrict__ meta, int xk_G, int edge_drain, int bx_per, int bx_wide,
+                                                            int all_slabs) {
     nedge = nedge < 0 ? -nedge : min(nedge, (meta[EAGCN_META_T] + 15) / 16);   // edge-gradient workgroups that had rows (< 0: all wrote)
     // split-K partials actually written: gemm.hip writes eff_splits of them; the plane GEMM (gemm_bx3.hip) passes its slab count
     // negated and writes bx3_used_splits() of them
@@ -655,6 +656,7 @@ __global__ __launch_bounds__(256) void unpack_grads_kernel(GradPtrs gp, ParamPtr
     const int bxm = bx_wide ? BX3W_BM : BX3_BM, bxn = bx_wide ? BX3W_BN : BX3_BN;
     nsplit = nsplit < 0 ? bx3_used_splits_wave(-nsplit, meta[EAGCN_META_T], ((ld_in + bxm - 1) / bxm) * ((fp + bxn - 1) / bxn),
                                           bx_per > 0 ? ((meta[EAGCN_META_T] + bxm - 1) / bxm) * ((ld_in + bxn - 1) / bxn) : 0, max(1, (fp + 31) >> 5), bx_per)
+                        : all_slabs ? nsplit                         // (lagg_dw.hip: one slab per workgroup row, every one written)
                         : max(1, min(nsplit, meta[EAGCN_META_T] >> 7));
     if ((int)blockIdx.x < wblocks) {
         // split-K slabs: FOUR lanes per group of four adjacent elements (one 16-byte load per slab: a wavefront covers 256 contiguous
@@ -1034,6 +1036,9 @@ struct LayerRoute {
     BwdProd bwd_prod = BWD_NONE; bool bwd_split_x = false;
     bool defer_drain = false;                                    // the edge reduction is left to the next layer's first kernel
     bool dh_given = false;                                       // no reduction pass: dH and its sums came from the layer above's dX product
+    // a refinement below BWD_TILED_SEPARATE (first layer, no dX asked): dWcat leaves the transposed aggregation's epilogue as dw_ny
+    // slabs (lagg_dw.hip) -- no dP, no product launch; the slabs live in the dWcat area, or in the dP area this route leaves free
+    bool dw_fused = false; int dw_ny = 0; bool dw_in_dp = false;
     bool bn2_staged() const { return bn2 >= BN2_STAGED_FROM_DH; }
     bool bwd_planes() const { return bwd_prod >= BWD_PLANES_PAIR && bwd_prod <= BWD_PLANES_DX; }
 };
@@ -1053,6 +1058,11 @@ static bool bn_bwd_two_pass(bool weighted) {
 static bool gemm3_layer(int ld_in) {
     return sw_gemm3() && ld_in >= 128 && gemm_mode() != 2;       // (the bf16 mode runs on the LDS-tiled kernels of gemm.hip)
 }
+// EAGCN_FIRST_LAYER_FUSED=0 in the environment / eagcn_set_first_layer_fused(0): the first layer's weight gradient stays a launch of its own
+static int g_first_layer_fused = env_flag("EAGCN_FIRST_LAYER_FUSED", true) ? 1 : 0;
+static long g_first_layer_fused_taken = 0;
+static int32_t g_first_layer_fused_last[3] = {0, 0, 0};      // of the last such call: slabs (= the grid's y extent), slabs in the dP area, uncapped y extent
+static bool first_layer_fused_enabled() { return g_first_layer_fused != 0; }
 
 static LayerRoute plan_layer(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const LayerDims& d,
                              PlanAsk ask) {
@@ -1122,6 +1132,17 @@ static LayerRoute plan_layer(const eagcn_batch* b, const eagcn_layer_params* p, 
     else r.bwd_prod = ask.has_dx ? BWD_TILED_PAIR : BWD_TILED_SEPARATE;
     // nothing but the edge reduction is left for this layer (no dW slabs to sum): the next layer's first backward kernel does it
     r.defer_drain = ask.has_drain_out && r.edge_atomic && r.bwd_prod == BWD_G3_SCATTER;
+    // the first layer's weight gradient inside the aggregation launch: the plain transposed kernel (dY' or dH staged, not the
+    // upstream-gradient forms), exact fp32 products in both places, at most 32 input columns (one pair of 16-row MFMA tiles)
+    const bool plain_staging = r.bn2 != BN2_STAGED_FROM_UPSTREAM && r.bn2 != BN2_STAGED_ROWMASK && r.bn2 != BN2_STAGED_FROM_READOUT;
+    if (first_layer_fused_enabled() && r.bwd_prod == BWD_TILED_SEPARATE && r.edge == EDGE_WITH_LAGG && r.bwd_agg == AGG_LAGG &&
+        plain_staging && d.ld_in <= 32 && gemm_mode() != 1 && gemm_mode() != 2 && w->x) {
+        const long cap_w = std::max(std::max(d.nsplit, G3_XSEG), d.np ? d.bx_splits : 1);       // (carve_layer: slabs of the dWcat area)
+        const long cap_p = (long)(((size_t)std::max(b->T, 1) * d.fp) / d.wslab);               // ... and of the dP area
+        r.dw_fused = true;
+        r.dw_ny = (int)std::max<long>(1, std::min<long>(lagg_bwd_grid_y(b, d.vc), std::max(cap_w, cap_p)));
+        r.dw_in_dp = r.dw_ny > cap_w;
+    }
     return r;
 }
 
@@ -1338,6 +1359,18 @@ extern "C" int eagcn_set_hidden_bn_sums(int on) {
     g_hidden_bn_sums = on ? 1 : 0;
     return old;
 }
+/* layer backward calls (captured ones count when they are captured) whose weight gradient left the transposed aggregation's epilogue, since the last reset */
+extern "C" long eagcn_first_layer_fused_taken(int reset) {
+    const long n = g_first_layer_fused_taken;
+    if (reset) g_first_layer_fused_taken = 0;
+    return n;
+}
+extern "C" void eagcn_first_layer_fused_last(int32_t out[3]) { memcpy(out, g_first_layer_fused_last, sizeof(g_first_layer_fused_last)); }
+extern "C" int eagcn_set_first_layer_fused(int on) {
+    const int old = g_first_layer_fused;
+    g_first_layer_fused = on ? 1 : 0;
+    return old;
+}
 bool eagcn::layer_hidden_sums_route(const eagcn_batch* b, const eagcn_layer_params* up, const eagcn_layer_params* low, BxBnEpi* ep) {
     if (!g_hidden_bn_sums || !b || !up || !low || b->T <= 0 || low->structure != EAGCN_STRUCT_CONCATE || !low->training) return false;
     void* const some = reinterpret_cast<void*>(static_cast<uintptr_t>(4096));
@@ -1527,6 +1560,11 @@ static int bwd_aggregate(LayerBwd& c) {
         a.bn_tab = w->bn; a.bn_cc = (c.o.input_only && !c.p->training) ? nullptr : sc.cc; a.bn_fp = d.fp;
     }
     if (r.dh_given) { a.src = c.dxout; a.lds = d.ldo; }          // dH as the layer above's dX product left it (Concate: ldo == fp)
+    if (r.dw_fused) {            // no dP: the weight gradient leaves the epilogue as one slab per workgroup row
+        ++g_first_layer_fused_taken;
+        g_first_layer_fused_last[0] = r.dw_ny; g_first_layer_fused_last[1] = r.dw_in_dp ? 1 : 0; g_first_layer_fused_last[2] = lagg_bwd_grid_y(b, d.vc);
+        a.dst = nullptr; a.fx = w->x; a.fx_ld = d.ld_in; a.dw = r.dw_in_dp ? sc.dP : sc.dWcat; a.dw_slab = d.wslab; a.dw_ny = r.dw_ny;
+    }
     if (r.bn2 == BN2_STAGED_FROM_UPSTREAM || r.bn2 == BN2_STAGED_ROWMASK || r.bn2 == BN2_STAGED_FROM_READOUT) {
         // ... and dH before it, from the upstream gradient
         a.src = c.dg ? sc.dY : c.dxout; a.lds = d.ldo;
@@ -1557,6 +1595,10 @@ static int bwd_products(LayerBwd& c, const LayerOperands& o) {
     dsc.in = c.in;
     int rc;
     c.nsplit = d.nsplit;
+    if (c.r.dw_fused) {          // the transposed aggregation wrote every one of its slabs: nothing to launch
+        c.nsplit = c.r.dw_ny;
+        return EAGCN_OK;
+    }
     switch (c.r.bwd_prod) {
     case BWD_PLANES_DX: return launch_bx3(bq.bx, nullptr, d.np, s, c.gemm_work, PROF_GEMM, bx3_pick_wide(bq.bx, nullptr, b->t_hint));
     case BWD_TILED_DX: return launch_gemm(gq.gx, s);
@@ -1622,10 +1664,12 @@ static int bwd_unpack(LayerBwd& c) {
     const bool shared = b->T > 0 && c.r.edge_atomic;                    // shared accumulators: zeroed again by the threads that read them
     const int nedge = b->T > 0 ? (shared ? -EDGE_COPIES : edge_grid_x(b)) : 0;
     ProfScope psu(PROF_PACK, c.s);
-    unpack_grads_kernel<<<wblocks + cdiv(p->K * EDGE_SLAB, 16), 256, 0, c.s>>>(c.gp, c.pp, d.vc, c.in, d.ld_in, d.fp, sc.dWcat,
+    unpack_grads_kernel<<<wblocks + cdiv(p->K * EDGE_SLAB, 16), 256, 0, c.s>>>(c.gp, c.pp, d.vc, c.in, d.ld_in, d.fp,
+                                                                                  (c.r.dw_fused && c.r.dw_in_dp) ? sc.dP : sc.dWcat,
                                                                                   c.bx_slabs ? -c.nsplit : c.nsplit, d.wslab,
                                                                                   shared ? sc.eacc : sc.datt, nedge, sc.pk.rsig,
-                                                                                  wblocks, b->meta, c.xk_G, shared ? 1 : 0, c.bx_per, c.bx_wide);
+                                                                                  wblocks, b->meta, c.xk_G, shared ? 1 : 0, c.bx_per, c.bx_wide,
+                                                                                  c.r.dw_fused ? 1 : 0);        // (the aggregation's epilogue wrote every one of its slabs, whatever the row count)
     EAGCN_LAUNCH_CHECK();
     return EAGCN_OK;
 }

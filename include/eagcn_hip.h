@@ -708,6 +708,20 @@ int eagcn_set_hidden_bn_sums(int on);
 /* How many layer backward calls took that route since the last reset (a captured call counts when it is captured); reset != 0 clears
  * the count.  For tests. */
 long eagcn_hidden_bn_sums_taken(int reset);
+/* The weight gradient of a layer of at most 32 input columns whose input gradient is not asked for (the first layer of a model in
+ * training; route values BWD_TILED_SEPARATE with the bond-list aggregation and its edge gradients, exact fp32 products): 1 (default;
+ * EAGCN_FIRST_LAYER_FUSED=0 in the environment presets 0): formed in the epilogue of the transposed aggregation, which then neither
+ * stores dP nor is followed by a product launch; the route values eagcn_layer_route shows stay what they are
+ * | 0: dP is stored and the split-K product is a launch of its own.  Returns the previous setting.  For tests and A/B runs; set it
+ * between steps, before a graph is captured (a captured graph keeps its route). */
+int eagcn_set_first_layer_fused(int on);
+/* How many layer backward calls took that route since the last reset (a captured call counts when it is captured); reset != 0 clears
+ * the count.  For tests. */
+long eagcn_first_layer_fused_taken(int reset);
+/* ... and of the last such call: out[0] = slabs written (the launch's y extent), out[1] = 1 when they live in the dP area of the
+ * scratch block (more slabs than the dWcat area holds), out[2] = the y extent the launch would have had without the slab capacity's
+ * cap (larger than out[0]: workgroup rows walk several blocks).  For tests. */
+void eagcn_first_layer_fused_last(int32_t out[3]);
 /* ... of the TN problem (M, N, K) of eagcn_gemm_bx3_pair: its chunks are sized against the NT problem (M0, N0, K0) of the launch */
 int eagcn_bx3_pair_used_splits(int splits, int M, int N, int K, int M0, int N0, int K0);
 int eagcn_gemm_bx3(int tn, int M, int N, int K, const uint16_t* A, size_t a_pstride, int lda, int a_rows, const uint16_t* B,
