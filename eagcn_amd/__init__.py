@@ -3,9 +3,10 @@ from .layers import (GAT, AFM_BatchNorm, Ave_multi_view, Dense, Diff_Pooling, Gr
                      GraphConv_base, GraphConv_block, GraphConv_Layer, Vanilla_GCN)
 from .models import EAGCN, Concate_GCN, Weighted_GCN, weights_init  # noqa: F401
 from .training import EvalBuffers, EvalResult, evaluate  # noqa: F401
-from .analysis import KMeansResult, RepBuffers, confusion_matrix, dump_atom_rep, kmeans  # noqa: F401
+from .analysis import (KMeansResult, PCAResult, RepBuffers, TSNEResult, confusion_matrix, dump_atom_rep, kmeans, pca,  # noqa: F401
+                       subsample, tsne)
 
 __all__ = ['EAGCN', 'Concate_GCN', 'Weighted_GCN', 'GraphConv_Layer', 'GraphConv_block', 'GraphConv_base',
            'AFM_BatchNorm', 'Ave_multi_view', 'Dense', 'Vanilla_GCN', 'GAT', 'GraphAttentionLayer', 'Diff_Pooling',
            'weights_init', 'EvalBuffers', 'EvalResult', 'evaluate', 'RepBuffers', 'dump_atom_rep', 'kmeans', 'KMeansResult',
-           'confusion_matrix']
+           'confusion_matrix', 'pca', 'PCAResult', 'tsne', 'TSNEResult', 'subsample']

@@ -335,6 +335,17 @@ SIGNATURES = {
     'eagcn_kmeans_iterate': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, C.c_int, _fp, C.c_size_t, _fp]),
     'eagcn_kmeans_finish': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, C.c_int, _fp, C.c_size_t, _fp]),
     'eagcn_kmeans_assign': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp, _fp, C.c_size_t, _fp]),
+    'eagcn_sqdist': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, _fp, _fp]),
+    'eagcn_tsne_workspace_bytes': (C.c_size_t, [C.c_int64]),
+    'eagcn_tsne_affinities': (C.c_int, [_fp, C.c_int64, C.c_double, _fp, C.c_int, _fp, _fp, _fp, C.c_size_t, _fp]),
+    'eagcn_tsne_gradient': (C.c_int, [_fp, C.c_int, _fp, C.c_int64, C.c_float, C.c_int, _fp, _fp, _fp, C.c_size_t, _fp]),
+    'eagcn_tsne_begin': (C.c_int, [_fp, C.c_int, C.c_int64, _fp, C.c_float, C.c_float, C.c_int, C.c_int, C.c_double, _fp, C.c_size_t,
+                                   _fp]),
+    'eagcn_tsne_iterate': (C.c_int, [_fp, C.c_int, C.c_int64, _fp, C.c_size_t, _fp]),
+    'eagcn_tsne_finish': (C.c_int, [_fp, C.c_int, C.c_int64, _fp, C.c_size_t, _fp]),
+    'eagcn_pca_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int]),
+    'eagcn_pca_cov': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, _fp, _fp, _fp, C.c_size_t, _fp]),
+    'eagcn_pca_project': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, _fp]),
     'eagcn_prof_enable': (None, [C.c_int]),
     'eagcn_prof_reset': (None, []),
     'eagcn_prof_ntags': (C.c_int, []),

@@ -9,7 +9,11 @@ last layer behind a device-side row counter (csrc/reps.hip: eagcn_rep_gather; th
 host until ``finish``), and Lloyd's iterations run as HIP kernels that read every row once per iteration (eagcn_kmeans_*).
 
 One documented deviation from scikit-learn: a cluster that runs EMPTY keeps its centroid (``n_empty`` counts them); scikit-learn
-relocates it to the point farthest from its centre."""
+relocates it to the point farthest from its centre.
+
+The second half of that analysis, the two-dimensional embeddings of tsnes.py and mol_to_vec_plot.py, is here as well: ``pca`` and an
+EXACT ``tsne`` (csrc/embed.hip) over the rows of the dump -- ``tsne(d.X[subsample(d.subtype, classes, cap)])`` for atoms,
+``tsne(d.graph_rep)`` for molecules -- without a copy of the rows to the host."""
 import ctypes as C
 from collections import namedtuple
 
@@ -273,3 +277,178 @@ def confusion_matrix(y_true, labels, n_true, k):
     if y.numel() != c.numel():
         raise ValueError('confusion_matrix: %d true classes for %d labels' % (y.numel(), c.numel()))
     return torch.bincount(y * int(k) + c, minlength=int(n_true) * int(k)).view(int(n_true), int(k))
+
+
+# ---- PCA and exact t-SNE (csrc/embed.hip) ------------------------------------------------------------------------------------------
+
+PCAResult = namedtuple('PCAResult', 'components explained_variance mean embedding')
+TSNEResult = namedtuple('TSNEResult', 'embedding kl_divergence n_iter stop_reason learning_rate betas P')
+STOP_REASONS = {0: 'running', 1: 'max_iter', 2: 'no_progress', 3: 'min_grad_norm'}      # EAGCN_TSNE_STOP_* of include/eagcn_hip.h
+EXPLORATION_ITERS = 250                                                                  # TS_EXPLORE of csrc/embed.hip
+
+
+def _rows(X, what):
+    """X as the kernels take it: fp32 device rows with unit column stride (ld >= F).  (X, n, F, ld)"""
+    if not isinstance(X, torch.Tensor) or not X.is_cuda or X.dtype != torch.float32 or X.dim() != 2:
+        raise L.EagcnHipError('%s: X must be a float32 [n, F] tensor on the MI355X (eagcn_amd has no CPU path)' % what)
+    n, F = X.shape
+    if X.stride(1) != 1 or X.stride(0) < F:
+        X = X.contiguous()
+    return X, int(n), int(F), int(X.stride(0))
+
+
+def sqdist(X):
+    """[n, n] fp32 squared Euclidean distances between the rows of X: direct sums of squared differences (eagcn_sqdist)"""
+    X, n, F, ld = _rows(X, 'sqdist')
+    D = torch.empty((n, n), dtype=torch.float32, device=X.device)
+    L.check(L.load().eagcn_sqdist(X.data_ptr(), n, F, ld, D.data_ptr(), _stream()), 'eagcn_sqdist')
+    return D
+
+
+def pca_cov(X):
+    """(mean [F], cov [F, F]) in fp64 on the device (eagcn_pca_cov); no host read"""
+    X, n, F, ld = _rows(X, 'pca')
+    lib = L.load()
+    ws = torch.empty(max(lib.eagcn_pca_workspace_bytes(n, F), 256), dtype=torch.uint8, device=X.device)
+    mean = torch.empty(F, dtype=torch.float64, device=X.device)
+    cov = torch.empty((F, F), dtype=torch.float64, device=X.device)
+    L.check(lib.eagcn_pca_cov(X.data_ptr(), n, F, ld, mean.data_ptr(), cov.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), 'eagcn_pca_cov')
+    return mean, cov
+
+
+def pca(X, n_components=2):
+    """sklearn.decomposition.PCA(n_components, svd_solver='full') of the device rows X [n, F]: column means and covariance on the
+    device (eagcn_pca_cov), the F x F eigen-decomposition ONCE on the host in fp64 (torch.linalg.eigh: the one host synchronisation of
+    this call), the projection on the device (eagcn_pca_project).  Signs as svd_flip(u_based_decision=False): the entry of largest
+    magnitude of every component is positive.  PCAResult(components [k, F] fp32, explained_variance [k] fp64, mean [F] fp64,
+    embedding [n, k] fp32), all on the device."""
+    k = int(n_components)
+    X, n, F, ld = _rows(X, 'pca')
+    mean, cov = pca_cov(X)
+    lam, vec = torch.linalg.eigh(cov.cpu())
+    lam, vec = lam.flip(0)[:k], vec.flip(1)[:, :k].t().contiguous()               # descending, [k, F]
+    big = vec.abs().argmax(dim=1)
+    vec = vec * torch.sign(vec[torch.arange(vec.shape[0]), big]).unsqueeze(1)
+    comp = vec.to(device=X.device, dtype=torch.float32).contiguous()
+    emb = torch.empty((n, comp.shape[0]), dtype=torch.float32, device=X.device)
+    L.check(L.load().eagcn_pca_project(X.data_ptr(), n, F, ld, mean.data_ptr(), comp.data_ptr(), k, emb.data_ptr(), _stream()),
+            'eagcn_pca_project')
+    return PCAResult(comp, lam.clamp_min(0.0).to(X.device), mean, emb)
+
+
+class _TSNEProblem:
+    """The joint probabilities P [n, ldp] (ldp = pad4(n): 16-byte rows) and a t-SNE workspace with typed views into it."""
+
+    def __init__(self, n, device):
+        self.lib = L.load()
+        self.n, self.ldp = int(n), L.pad4(n)
+        nbytes = self.lib.eagcn_tsne_workspace_bytes(self.n)
+        self.ws = torch.empty(max(nbytes, 512), dtype=torch.uint8, device=device)
+        self.state_i = self.ws[0:16].view(torch.int32)             # done | n_iter | reason | best_iter
+        self.state_d = self.ws[16:40].view(torch.float64)          # best_err | last_kl | last_gnorm
+        part = _a256(8 * self.n)
+        self.Y, self.U, self.gains = ((self.ws[256 + j * part:256 + j * part + 8 * self.n].view(torch.float32).view(self.n, 2)
+                                       if nbytes else None) for j in range(3))
+        self.P = self.betas = self.steps = None
+
+    def _ws(self):
+        return (self.ws.data_ptr(), self.ws.numel(), _stream())
+
+    def affinities(self, D, perplexity):
+        """P, betas [n] fp64 and the search's step counts [n] int32 from squared distances D [n, n] (fp32, contiguous)"""
+        self.P = torch.empty((self.n, self.ldp), dtype=torch.float32, device=D.device)
+        self.betas = torch.empty(self.n, dtype=torch.float64, device=D.device)
+        self.steps = torch.empty(self.n, dtype=torch.int32, device=D.device)
+        L.check(self.lib.eagcn_tsne_affinities(D.data_ptr(), self.n, float(perplexity), self.P.data_ptr(), self.ldp, self.betas.data_ptr(),
+                                               self.steps.data_ptr(), *self._ws()), 'eagcn_tsne_affinities')
+
+    def set_P(self, P):
+        """a joint P [n, n] computed elsewhere (tests): copied into the padded layout"""
+        self.P = torch.zeros((self.n, self.ldp), dtype=torch.float32, device=P.device)
+        self.P[:, :self.n] = P
+
+    def gradient(self, Y, alpha, compute_kl=True):
+        """(grad [n, 2] fp32, out [3] fp64 = Z | KL | |grad|) of one stand-alone gradient pass at Y [n, 2]"""
+        Y = Y.to(torch.float32).contiguous()
+        grad = torch.empty((self.n, 2), dtype=torch.float32, device=Y.device)
+        out = torch.empty(3, dtype=torch.float64, device=Y.device)
+        L.check(self.lib.eagcn_tsne_gradient(self.P.data_ptr(), self.ldp, Y.data_ptr(), self.n, float(alpha), int(bool(compute_kl)),
+                                             grad.data_ptr(), out.data_ptr(), *self._ws()), 'eagcn_tsne_gradient')
+        return grad, out
+
+    def begin(self, Y0, early_exaggeration, learning_rate, max_iter, n_iter_without_progress, min_grad_norm):
+        Y0 = Y0.to(torch.float32).contiguous()
+        L.check(self.lib.eagcn_tsne_begin(self.P.data_ptr(), self.ldp, self.n, Y0.data_ptr(), float(early_exaggeration), float(learning_rate),
+                                          int(max_iter), int(n_iter_without_progress), float(min_grad_norm), *self._ws()), 'eagcn_tsne_begin')
+
+    def iterate(self):
+        L.check(self.lib.eagcn_tsne_iterate(self.P.data_ptr(), self.ldp, self.n, *self._ws()), 'eagcn_tsne_iterate')
+
+    def finish(self):
+        L.check(self.lib.eagcn_tsne_finish(self.P.data_ptr(), self.ldp, self.n, *self._ws()), 'eagcn_tsne_finish')
+
+
+def tsne(X, perplexity=30.0, early_exaggeration=12.0, learning_rate='auto', max_iter=1000, n_iter_without_progress=300, min_grad_norm=1e-7,
+         init='pca', generator=None, sync_every=50):
+    """Exact two-dimensional t-SNE of the device rows X [n, F] (csrc/embed.hip; semantics in include/eagcn_hip.h: those of
+    sklearn.manifold.TSNE(method='exact', n_components=2) with the deviations listed there).  Distances, affinities and every
+    iteration run on the device; the host enqueues iterations in groups of `sync_every` and reads the `done` word once per group --
+    iterations behind a stop are no-ops on the device, so the result does not depend on `sync_every`.
+      learning_rate 'auto': max(n / early_exaggeration / 4, 50).
+      init 'random': 1e-4 N(0, 1) drawn on the device with `generator`; 'pca': this module's pca(X, 2) scaled to a standard deviation
+        of 1e-4 in the first column (scikit-learn uses its randomized solver there: equal in kind, not in bits); or a [n, 2] tensor.
+    Returns TSNEResult(embedding [n, 2], kl_divergence (of the final embedding against the un-exaggerated P), n_iter, stop_reason,
+    learning_rate, betas [n] fp64, P [n, n] fp32 (a view of the padded matrix)); the tensors stay on the device."""
+    X, n, F, ld = _rows(X, 'tsne')
+    max_iter, sync_every = int(max_iter), max(1, int(sync_every))
+    if max_iter < 1:
+        raise ValueError('tsne: max_iter must be at least 1')
+    lr = max(n / float(early_exaggeration) / 4.0, 50.0) if learning_rate == 'auto' else float(learning_rate)
+    if isinstance(init, torch.Tensor):
+        if tuple(init.shape) != (n, 2) or not init.is_cuda:
+            raise L.EagcnHipError('tsne: init must be a device tensor of shape [n, 2] = [%d, 2]' % n)
+        Y0 = init.to(torch.float32)
+    elif init == 'random':
+        Y0 = 1e-4 * torch.randn((n, 2), dtype=torch.float32, device=X.device, generator=generator)
+    elif init == 'pca':
+        Y0 = pca(X, 2).embedding
+        Y0 = Y0 / Y0[:, 0].std(unbiased=False) * 1e-4
+    else:
+        raise ValueError("tsne: init must be a [n, 2] tensor, 'random' or 'pca'")
+    p = _TSNEProblem(n, X.device)
+    p.affinities(sqdist(X), perplexity)
+    p.begin(Y0, early_exaggeration, lr, max_iter, n_iter_without_progress, min_grad_norm)
+    it = 0
+    while it < max_iter:
+        m = min(sync_every, max_iter - it)
+        for _j in range(m):
+            p.iterate()
+        it += m
+        if int(p.state_i[0].item()):                         # the one host read of a group
+            break
+    p.finish()
+    _done, n_iter, reason, _best = p.state_i.tolist()
+    return TSNEResult(p.Y.clone(), float(p.state_d[1].item()), n_iter, STOP_REASONS.get(reason, str(reason)), lr, p.betas, p.P[:, :n])
+
+
+def subsample(labels, classes, cap, generator=None):
+    """Row indices (int64, ascending, on the device) of at most `cap` rows of every class in `classes`: the reference's selection in
+    front of its embeddings (tsnes.py:62-86, 217-225).  Exactly min(count, cap) rows per class are kept, chosen uniformly at random
+    with `generator` (the reference keeps each row with probability cap / count and so only approximates the cap).  torch ops only,
+    no host read except the size of the result, which torch.nonzero needs."""
+    lab = torch.as_tensor(labels)
+    if not lab.is_cuda:
+        raise L.EagcnHipError('subsample: labels must be a device tensor (eagcn_amd has no CPU path)')
+    lab = lab.view(-1).to(torch.int64)
+    cls = torch.as_tensor(classes, device=lab.device, dtype=torch.int64).view(-1)
+    member = (lab.unsqueeze(1) == cls.unsqueeze(0)).any(dim=1)
+    key = torch.rand(lab.numel(), dtype=torch.float64, device=lab.device, generator=generator)
+    # sort by (class, random key): a row's rank within its class is its position minus the first position of the class
+    order = torch.argsort(key)
+    order = order[torch.argsort(lab[order], stable=True)]
+    sl = lab[order]
+    pos = torch.arange(lab.numel(), device=lab.device)
+    first = torch.searchsorted(sl, sl, right=False)
+    keep = torch.zeros(lab.numel(), dtype=torch.bool, device=lab.device)
+    keep[order] = (pos - first) < int(cap)
+    return torch.nonzero(keep & member).view(-1)

@@ -660,6 +660,66 @@ int eagcn_kmeans_finish(const float* X, int64_t n, int F, int ld, int k, void* w
 int eagcn_kmeans_assign(const float* X, int64_t n, int F, int ld, const float* centers, int k, int32_t* labels, float* mind,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- exact t-SNE and PCA of device rows (the reference's tsnes.py / mol_to_vec_plot.py; csrc/embed.hip), on the caller's stream, no
+ * floating-point atomics, every sum folded in a fixed order: results are bit-identical from run to run.  Semantics are those of
+ * sklearn.manifold.TSNE(method='exact', n_components=2, metric='euclidean') and sklearn.decomposition.PCA(svd_solver='full') (1.7.2)
+ * with the deviations marked DEVIATION below.  Envelope: X fp32 with unit column stride, ld >= F, 1 <= F <= 1024; t-SNE and distances
+ * 17 <= n <= 32768; PCA 17 <= n < 2^31, k <= min(8, F) components.  Anything else returns EAGCN_ERR_ARG before any HIP call.
+ *
+ *   eagcn_sqdist: D[n][n] fp32, D_ij = sum_f (x_if - x_jf)^2 as direct differences in a fixed order (never the Gram identity); the
+ *     diagonal is exactly 0 and D exactly symmetric.
+ *   eagcn_tsne_affinities: scikit-learn's _binary_search_perplexity and _joint_probabilities.  Per row i, in fp64 on the fp32 distances:
+ *     beta = 1, bisected for at most 100 evaluations of  s = sum_{j != i} exp(-D_ij beta) (1e-8 where it is 0),
+ *     H = log s + beta sum_j D_ij exp(-D_ij beta) / s, stopping when |H - log perplexity| <= 1e-5; C_ij = exp(-D_ij beta) / s.  Then
+ *     P_ij = max((C_ij + C_ji) / sum(C + C^T), DBL_EPSILON), P_ii = 0, stored in fp32 as P[n][ldp]: ldp a multiple of 4, >= n, P 16-byte
+ *     aligned; the columns n .. ldp - 1 are written as 0.  betas[n] fp64: the precision of the LAST EVALUATION of every row;
+ *     steps[n] int32 (may be NULL): evaluations made.  D is read as [n][n]; 0 < perplexity < n.  The workspace (as below) is scratch.
+ *   eagcn_tsne_gradient: one evaluation of the objective at Y[n][2] (fp32, 16-byte aligned) with the exaggeration alpha:
+ *     w_ij = 1 / (1 + |y_i - y_j|^2); per row the fp32 sums over j != i  a_i = sum alpha P_ij w_ij (y_i - y_j),
+ *     r_i = sum w_ij^2 (y_i - y_j), z_i = sum w_ij; Z = sum_i z_i in fp64; grad_i = 4 (a_i - r_i / Z) -> grad[n][2] fp32.
+ *     out[3] doubles = Z | KL | |grad|_2, where, if compute_kl, KL = sum_{i != j} q log max(q, eps) + sum q log(1 + |y_i - y_j|^2)
+ *     + log Z sum q with q = alpha P_ij and eps = DBL_EPSILON, in fp64 (NaN otherwise).  DEVIATION: scikit-learn clamps Q_ij = w_ij / Z
+ *     below at eps inside the logarithm; this form does not.
+ *   eagcn_tsne_begin / iterate / finish: scikit-learn's two-stage _gradient_descent on the device.  Iteration it (0-based) runs with
+ *     alpha = early_exaggeration and momentum 0.5 while it < 250, then alpha = 1, momentum 0.8 and update / gains reset to 0 / 1 at
+ *     it = 250.  Element-wise in fp32, without contraction:  gains += 0.2 where update * grad < 0, else gains *= 0.8; gains =
+ *     max(gains, 0.01); grad *= gains; update = momentum update - learning_rate grad; Y += update.  Every 50th iteration
+ *     ((it + 1) % 50 == 0) the divergence (against alpha P, as scikit-learn reports it) and the norm of the GAINED gradient are formed:
+ *     a divergence below the best one so far is recorded with its iteration, otherwise the fit stops when it - best_iter exceeds the
+ *     window (250 while it < 250, n_iter_without_progress after; the best is reset at it = 250); it stops when the norm is at most
+ *     min_grad_norm; and it stops when n_iter reaches max_iter.  DEVIATIONS: a stop in the first stage ends the FIT (scikit-learn goes
+ *     on with the second stage); n_iter counts iterations made (scikit-learn's n_iter_ is the index of the last one); max_iter may
+ *     be below 250.  eagcn_tsne_iterate enqueues ONE iteration (four launches); every launch returns at once when `done` is set, so
+ *     iterations enqueued behind a stop change nothing and the host may read `done` as rarely as it likes.  eagcn_tsne_finish leaves
+ *     in last_kl the divergence of the FINAL embedding against the un-exaggerated P (DEVIATION: scikit-learn's kl_divergence_ is the
+ *     value of its last check).
+ *   workspace: 256-byte aligned, at least eagcn_tsne_workspace_bytes(n) bytes (0 outside the envelope), written by eagcn_tsne_begin:
+ *       bytes 0 .. 63   state: int32 done | n_iter | reason | best_iter, double best_err | last_kl | last_gnorm,
+ *                       float early_exaggeration | learning_rate, int32 max_iter | n_iter_without_progress, double min_grad_norm
+ *       bytes 256 ..    the embedding Y [n][2] fp32, then update [n][2] and gains [n][2] fp32, each part rounded up to a multiple of
+ *                       256 bytes; the rest is internal.
+ *   eagcn_pca_cov: mean[F] fp64 (column sums in fp64, per workgroup and then over the workgroups in order) and cov[F][F] fp64 =
+ *     (X - mean)^T (X - mean) / (n - 1): products of the fp32-centred rows summed in fp32 over 256 rows, then in fp64; exactly
+ *     symmetric.  workspace: 256-byte aligned, eagcn_pca_workspace_bytes(n, F) bytes.  The eigen-decomposition is the caller's.
+ *   eagcn_pca_project: out[n][k] fp32 = (X - mean) components^T, components [k][F] fp32. */
+#define EAGCN_TSNE_STOP_MAX_ITER 1
+#define EAGCN_TSNE_STOP_NO_PROGRESS 2
+#define EAGCN_TSNE_STOP_GRAD_NORM 3
+int eagcn_sqdist(const float* X, int64_t n, int F, int ld, float* D, void* stream);
+size_t eagcn_tsne_workspace_bytes(int64_t n);
+int eagcn_tsne_affinities(const float* D, int64_t n, double perplexity, float* P, int ldp, double* betas, int32_t* steps, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int eagcn_tsne_gradient(const float* P, int ldp, const float* Y, int64_t n, float alpha, int compute_kl, float* grad, double* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int eagcn_tsne_begin(const float* P, int ldp, int64_t n, const float* Y0, float early_exaggeration, float learning_rate, int max_iter,
+                     int n_iter_without_progress, double min_grad_norm, void* workspace, size_t workspace_bytes, void* stream);
+int eagcn_tsne_iterate(const float* P, int ldp, int64_t n, void* workspace, size_t workspace_bytes, void* stream);
+int eagcn_tsne_finish(const float* P, int ldp, int64_t n, void* workspace, size_t workspace_bytes, void* stream);
+size_t eagcn_pca_workspace_bytes(int64_t n, int F);
+int eagcn_pca_cov(const float* X, int64_t n, int F, int ld, double* mean, double* cov, void* workspace, size_t workspace_bytes, void* stream);
+int eagcn_pca_project(const float* X, int64_t n, int F, int ld, const double* mean, const float* components, int k, float* out,
+                      void* stream);
+
 /* Matrix-core path of the layer products (the reference's torch.mm and its two autograd products, layers.py:40):
  *   0 = fp32 MFMA: exact fp32 products, a k-ordered fmaf chain (csrc/gemm3.hip);
  *   1 = every fp32 operand split into three bf16 pieces by the CONSUMER on its way into LDS, six bf16 MFMA products
