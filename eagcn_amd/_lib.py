@@ -302,6 +302,8 @@ SIGNATURES = {
                                        _fp, _fp, C.POINTER(LayerGrads), C.POINTER(HeadGrads), _fp]),
     'eagcn_model_backward_range': (C.c_int, [C.POINTER(Batch), C.POINTER(Model), _fp, _fp, C.c_size_t, _fp, C.c_size_t,
                                              _fp, _fp, C.POINTER(LayerGrads), C.POINTER(HeadGrads), C.c_int, C.c_int, C.c_int, _fp]),
+    'eagcn_model_route': (C.c_int, [C.POINTER(Batch), C.POINTER(Model), _fp, C.c_size_t, _fp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.POINTER(C.c_int32 * 16 * 4)]),
     'eagcn_model_input_scratch_bytes': (C.c_size_t, [C.POINTER(Batch), C.POINTER(Model)]),
     'eagcn_model_backward_input': (C.c_int, [C.POINTER(Batch), C.POINTER(Model), _fp, _fp, C.c_size_t, _fp, C.c_size_t,
                                              _fp, _fp, C.POINTER(LayerGrads), C.POINTER(HeadGrads), _fp, _fp]),

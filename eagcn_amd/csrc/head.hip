@@ -254,19 +254,77 @@ static bool fused_readout(const eagcn_model* m) {
     return env && m->fuse_readout && m->layer[m->n_layers - 1].structure == EAGCN_STRUCT_CONCATE;
 }
 
-// The top layer's BatchNorm backward takes its column sums from the read-out (readout.hip A1 / A2, head2.hip HeadTopSums, layer.hip
-// BN2_STAGED_FROM_READOUT) instead of a pass over its rows: a Concate top layer behind the fused read-out, sum / ave mode, training
-// with a local BatchNorm, on the route whose pass the sums replace (bond lists, N <= 256, no code books).  A pure function of the
-// model, the batch description and the switch: the forward, the head's backward and the layer's backward all ask it.
-static bool top_bn_sums(const eagcn_batch* b, const eagcn_model* m) {
-    if (!top_bn_sums_enabled() || m->n_layers < 1 || !fused_readout(m) || !m->training || m->stats_hook) return false;
-    if (m->molfp_mode != 0 && m->molfp_mode != 1) return false;
-    return layer_top_sums_route(b, &m->layer[m->n_layers - 1]);
-}
-
-// layer l's output is needed as plane images only: it has them, and the layer above reads nothing else (forward and backward)
-static bool hidden_planes_only(const eagcn_batch* b, const eagcn_model* m, const ModelSaved& sv, int l) {
-    return l + 1 < m->n_layers && sv.L[l].xout_planes && layer_reads_planes_only(b, &m->layer[l + 1]);
+// ---- the plan of a model call -----------------------------------------------------------------------------------------------------
+// What every layer of ONE engine call is handed and runs and what the layers hand each other, decided once from the buffers the call
+// runs on.  What the forward acts on (planes_only, skip_apply, top_formed) follows from (b, m, switches) alone, whatever a backward asks.
+struct ModelAsk { int layer_hi = -1, layer_lo = 0; bool has_dx0 = false, input_only = false; };    // (default: a forward -- no layer's backward)
+struct LayerPlan {
+    eagcn_layer_bufs w;          // x == nullptr behind a planes-only output
+    LayerRoute fwd, bwd;         // bwd: layers in [layer_lo, layer_hi].  dh_given: dH and its sums come from the layer above, whose
+                                 // dX product forms them (its carries_below; `below` describes this layer's tail pass to the kernel)
+    bool planes_only = false;    // no fp32 output: the layer above, planned WITHOUT it, runs both directions from the plane images
+    bool skip_apply = false;     // the top layer's output is applied by the fused read-out
+    BxBnEpi below = {};
+};
+// top_formed: the top layer's BatchNorm backward can take its column sums from the read-out (readout.hip A1 / A2, head2.hip HeadTopSums)
+// instead of a pass over its rows -- Concate behind the fused read-out, sum / ave, training with a local BatchNorm, on the route whose
+// pass they replace: the forward forms A1 / A2, the head's backward the slabs; the top layer USES them unless the call is input-only
+struct ModelPlan { LayerPlan L[4]; bool top_formed = false; };
+static ModelPlan plan_model(const eagcn_batch* b, const eagcn_model* m, const ModelSaved& sv, const ModelScratch& sc, const ModelAsk& ask) {
+    ModelPlan P{};
+    const int top = m->n_layers - 1;
+    PlanAsk full;                // (the backward of a training step, as far as the input's form goes)
+    full.has_dx = true;
+    for (int l = 0; l <= top; ++l) {
+        const LayerSaved& L = sv.L[l];
+        LayerPlan& Q = P.L[l];
+        eagcn_layer_bufs& w = Q.w;
+        w.P = L.P; w.Y = L.Y; w.rscale = L.rscale; w.bn = L.bn; w.xout = L.xout; w.pad_row = L.pad_row;
+        w.scratch = sc.layer; w.scratch_bytes = sc.layer_bytes; w.packed = L.packed; w.packed_bytes = L.packed_bytes;
+        w.stats_hook = m->stats_hook; w.stats_user = m->stats_user;
+        w.x_planes = l > 0 ? sv.L[l - 1].xout_planes : nullptr; w.xout_planes = L.xout_planes;
+        // planned with the plane images alone first; a layer that does not run on them in both directions gets the fp32 matrix
+        const bool try_planes = w.x_planes && planes_only_enabled();
+        w.x = l == 0 ? sv.x0 : try_planes ? nullptr : sv.L[l - 1].xout;
+        Q.fwd = plan_layer(b, &m->layer[l], &w, PlanAsk{});
+        if (try_planes) {
+            P.L[l - 1].planes_only = Q.fwd.fwd_prod == FWD_PLANES && plan_layer(b, &m->layer[l], &w, full).bwd_prod == BWD_PLANES_PAIR;
+            if (!P.L[l - 1].planes_only) { w.x = sv.L[l - 1].xout; Q.fwd = plan_layer(b, &m->layer[l], &w, PlanAsk{}); }
+        }
+    }
+    P.L[top].skip_apply = fused_readout(m);
+    // a layer's backward call in this model, but for what the layers hand each other
+    const float* dge = top_bn_gather_enabled() ? sc.top_dge : nullptr;
+    auto call_ask = [&](int l, const ModelAsk& k, bool top_sums) {
+        PlanAsk a;
+        a.has_dx = l > 0 || k.has_dx0; a.mol_grad = l == top; a.input_only = k.input_only; a.has_drain_out = l > k.layer_lo && !k.input_only;
+        a.top_sums = l == top && top_sums && !k.input_only; a.top_gather = a.top_sums && top_gather_ok(&m->layer[top], dge, m->head.f_in);
+        return a;
+    };
+    if (top_bn_sums_enabled() && P.L[top].skip_apply && m->training && m->layer[top].training && !m->stats_hook && (unsigned)m->molfp_mode <= 1u) {
+        const LayerRoute r = plan_layer(b, &m->layer[top], &P.L[top].w, call_ask(top, ModelAsk{top}, true));       // (the whole backward)
+        P.top_formed = r.bn2 == BN2_STAGED_FROM_READOUT && r.bwd_agg == AGG_LAGG && r.edge == EDGE_WITH_LAGG;
+    }
+    for (int l = ask.layer_hi; l >= ask.layer_lo; --l) {
+        LayerPlan& Q = P.L[l];
+        PlanAsk a = call_ask(l, ask, P.top_formed);
+        a.dh_given = l < ask.layer_hi && P.L[l + 1].bwd.carries_below;
+        // would the Concate layer below, in this call, take dH and its BatchNorm column sums from this layer's dX product?  (training,
+        // local BatchNorm; plan_layer answers whether THIS layer's product then carries the tail pass: the plane pair, 128 x 128 kernel)
+        if (l > ask.layer_lo && !ask.input_only && m->training && !m->stats_hook && sv.L[l].ld_in == sv.L[l - 1].fp) {
+            PlanAsk low = call_ask(l - 1, ask, false);
+            low.dh_given = true;
+            a.below = plan_layer(b, &m->layer[l - 1], &P.L[l - 1].w, low).dh_given;
+        }
+        Q.bwd = plan_layer(b, &m->layer[l], &Q.w, a);
+        if (Q.bwd.carries_below) {
+            const eagcn_layer_params* lo = &m->layer[l - 1];
+            const DropArgs dr = drop_args(lo->dropout, lo->training != 0, lo->seed, lo->seed_dev);
+            const LayerSaved& S = sv.L[l - 1];
+            Q.below = BxBnEpi{S.Y, S.fp, S.bn, S.fp, b->row_m, dr.on, dr.thr, dr.inv_keep, dr.seed, dr.seed_dev, sc.hid_slab};
+        }
+    }
+    return P;
 }
 
 }  // namespace eagcn
@@ -328,7 +386,7 @@ struct HeadPlan {
 };
 static HeadPlan head_plan(const eagcn_batch* b, const eagcn_model* m, const ModelSaved& sv, const ModelScratch& sc, float* out,
                           float* graph_rep, const float* dout, const float* dgraph_rep, const eagcn_head_grads* hg,
-                          const int64_t* size = nullptr) {
+                          const int64_t* size = nullptr, bool top_formed = false) {      // (ModelPlan.top_formed)
     HeadPlan P;
     P.size = size;
     const eagcn_head_params* h = &m->head;
@@ -381,7 +439,7 @@ static HeadPlan head_plan(const eagcn_batch* b, const eagcn_model* m, const Mode
     //  B = 1024 -- every packed row then gathers two molecule rows instead of one)
     P.bg = HeadGbn{B, F, sc.dgn, sv.g, sv.bn_g, P.sb_g, sc.dg, hg->d_gbn_w, hg->d_gbn_b, m->training};
     if (P.sync) { P.bg.cnt = cn_g; P.bg.gscale = gscale; }
-    if (top_bn_sums(b, m)) {
+    if (top_formed) {
         const eagcn_layer_params* last = &m->layer[m->n_layers - 1];
         const eagcn_layout lay = out_layout(last);
         P.bg.top = HeadTopSums{sv.top_a1, sv.top_a2, sc.top_slab, top_bn_slabs(B), eagcn_layer_fp(last), make_colmap(&lay), P.size, m->molfp_mode,
@@ -399,7 +457,7 @@ static HeadPlan head_plan(const eagcn_batch* b, const eagcn_model* m, const Mode
 // pack -> layers -> read-out (everything in front of the head): fills sv / sc
 static int model_forward_trunk(const eagcn_batch* b, const eagcn_model* m, const float* afm, const int64_t* size, void* saved,
                                size_t saved_bytes, void* scratch, size_t scratch_bytes, ModelSaved& sv, ModelScratch& sc,
-                               void* stream, const char* who) {
+                               ModelPlan& P, void* stream, const char* who) {
     hipStream_t s = (hipStream_t)stream;
     RC(check_model(b, m, who));
     EAGCN_CHECK_GEMM3(who);
@@ -420,27 +478,16 @@ static int model_forward_trunk(const eagcn_batch* b, const eagcn_model* m, const
     RC(gemm3_zero_job(sc.layer, sc.layer_bytes, sc.hst, (HEAD_COPIES + 1) * sc.n_hst + HEAD_WS, &zj));
     if (!m->input_packed)
         RC(eagcn_pack_rows(b, afm, layout_width(&m->layer[0].in), &m->layer[0].in, sv.x0, stream));
-    const float* x = sv.x0;
     {   // the parameters of every layer are re-laid by one launch
         const eagcn_layer_params* ps[4];
         void* pk[4];
         size_t pkb[4];
         for (int l = 0; l < m->n_layers; ++l) { ps[l] = &m->layer[l]; pk[l] = sv.L[l].packed; pkb[l] = sv.L[l].packed_bytes; }
-        RC(pack_params_all(b, ps, pk, pkb, m->n_layers, stream, &zj, &ho));
+        RC(pack_params_all(b, ps, pk, pkb, m->n_layers, stream, &zj, &ho));      // (checks every layer)
     }
-    for (int l = 0; l < m->n_layers; ++l) {
-        LayerSaved& L = sv.L[l];
-        eagcn_layer_bufs w;
-        memset(&w, 0, sizeof(w));
-        w.x = x; w.P = L.P; w.Y = L.Y; w.rscale = L.rscale; w.bn = L.bn; w.xout = L.xout; w.pad_row = L.pad_row;
-        w.scratch = sc.layer; w.scratch_bytes = sc.layer_bytes; w.packed = L.packed; w.packed_bytes = L.packed_bytes;
-        w.stats_hook = m->stats_hook; w.stats_user = m->stats_user;
-        w.x_planes = l > 0 ? sv.L[l - 1].xout_planes : nullptr; w.xout_planes = L.xout_planes;
-        // a hidden layer whose consumer reads plane images in both directions leaves no fp32 output (layer.hip bn_apply)
-        const bool po = hidden_planes_only(b, m, sv, l);
-        RC(layer_forward_impl(b, &m->layer[l], &w, stream, true, l == m->n_layers - 1 && fused_readout(m), po));
-        x = po ? nullptr : L.xout;
-    }
+    P = plan_model(b, m, sv, sc, ModelAsk{});
+    for (int l = 0; l < m->n_layers; ++l)
+        RC(layer_forward_impl(b, &m->layer[l], &P.L[l].w, stream, P.L[l].fwd, true, P.L[l].skip_apply, P.L[l].planes_only));
     const eagcn_layer_params* last = &m->layer[m->n_layers - 1];
     const LayerSaved& LL = sv.L[m->n_layers - 1];
     const eagcn_layout lay = out_layout(last);
@@ -456,7 +503,7 @@ static int model_forward_trunk(const eagcn_batch* b, const eagcn_model* m, const
         rb.size = size; rb.mode = m->molfp_mode; rb.g = sv.g; rb.F = F; rb.st = st_g;
         rb.cnt0 = st_g + 2 * F; rb.cnt1 = st_1 + 2 * n1; rb.cnt2 = st_2 + 2 * n2;
         rb.st_copies = copies; rb.st_stride = sc.n_hst;
-        if (top_bn_sums(b, m)) { rb.A1 = sv.top_a1; rb.A2 = sv.top_a2; }
+        if (P.top_formed) { rb.A1 = sv.top_a1; rb.A2 = sv.top_a2; }
         RC(readout_bn_forward(b, &lay, rb, stream));
     } else if (pad_sampled(m))
         RC(readout_forward_sampled(b, LL.xout, &lay, last, LL.bn + (size_t)LL.fp /* shift row of the BatchNorm table */, size,
@@ -523,7 +570,8 @@ extern "C" int eagcn_model_forward(const eagcn_batch* b, const eagcn_model* m, c
     EAGCN_CHECK_ARG(out && graph_rep, "eagcn_model_forward: null buffer");
     ModelSaved sv;
     ModelScratch sc;
-    RC(model_forward_trunk(b, m, afm, size, saved, saved_bytes, scratch, scratch_bytes, sv, sc, stream, "eagcn_model_forward"));
+    ModelPlan mp;
+    RC(model_forward_trunk(b, m, afm, size, saved, saved_bytes, scratch, scratch_bytes, sv, sc, mp, stream, "eagcn_model_forward"));
     const HeadPlan P = head_plan(b, m, sv, sc, out, graph_rep, nullptr, nullptr, nullptr);
     return head_forward_launches(m, P, stream);
 }
@@ -662,8 +710,9 @@ extern "C" int eagcn_model_forward_step(const eagcn_batch* b, const eagcn_model*
                         hg->d_bn1_b && hg->d_bn2_w && hg->d_bn2_b, "eagcn_model_forward_step: null head gradient");
     ModelSaved sv;
     ModelScratch sc;
-    RC(model_forward_trunk(b, m, afm, size, saved, saved_bytes, scratch, scratch_bytes, sv, sc, stream, "eagcn_model_forward_step"));
-    const HeadPlan P = head_plan(b, m, sv, sc, out, graph_rep, loss->dout, dgraph_rep, hg, size);
+    ModelPlan mp;
+    RC(model_forward_trunk(b, m, afm, size, saved, saved_bytes, scratch, scratch_bytes, sv, sc, mp, stream, "eagcn_model_forward_step"));
+    const HeadPlan P = head_plan(b, m, sv, sc, out, graph_rep, loss->dout, dgraph_rep, hg, size, mp.top_formed);
     const eagcn_head_params* h = &m->head;
     if (!P.sync && head_mid_ok(h->n_den2, h->nclass)) {
         // F1, F2 (counts the labelled entries on the way), then out + loss + d a2 as ONE launch, dense 3's weight gradient in
@@ -704,6 +753,22 @@ extern "C" int eagcn_model_backward(const eagcn_batch* b, const eagcn_model* m, 
                                       m->n_layers - 1, 0, stream);
 }
 
+// the blocks and the plan of a backward call (eagcn_model_backward_range, eagcn_model_backward_input, eagcn_model_route)
+static int plan_backward(const eagcn_batch* b, const eagcn_model* m, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                         int with_head, int layer_hi, int layer_lo, bool has_dx0, bool input_only, ModelSaved& sv, ModelScratch& sc,
+                         ModelPlan& P) {
+    EAGCN_CHECK_ARG(layer_hi < m->n_layers && layer_lo >= 0 && layer_lo <= layer_hi + 1,
+                    "eagcn_model_backward_range: layers %d..%d of %d", layer_hi, layer_lo, m->n_layers);
+    EAGCN_CHECK_ARG(!with_head || layer_hi == m->n_layers - 1 || layer_hi < layer_lo,
+                    "eagcn_model_backward_range: the head's backward is followed by the top layer");
+    EAGCN_CHECK_ARG(carve_saved(saved, b, m, &sv) <= saved_bytes, "eagcn_model_backward: saved block too small");
+    EAGCN_CHECK_ARG(carve_scratch(scratch, b, m, &sc) <= scratch_bytes, "eagcn_model_backward: scratch too small");
+    ModelAsk ask;
+    ask.layer_hi = layer_hi; ask.layer_lo = layer_lo; ask.has_dx0 = has_dx0; ask.input_only = input_only;
+    P = plan_model(b, m, sv, sc, ask);
+    return EAGCN_OK;
+}
+
 // the layer / head backward of eagcn_model_backward_range and eagcn_model_backward_input: dx0 != null: layer 0 also forms d(its
 // input), packed [T][ld_in]; input_only: lg == null, no parameter gradient of a layer is formed (hg: the caller's throw-away buffers)
 static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const int64_t* size, void* saved, size_t saved_bytes,
@@ -713,14 +778,10 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
     EAGCN_CHECK_ARG(saved && scratch && dout && (lg || input_only) && hg, "eagcn_model_backward: null buffer");
     EAGCN_CHECK_ARG(hg->d_den1_w && hg->d_den2_w && hg->d_den3_w && hg->d_gbn_w && hg->d_gbn_b && hg->d_bn1_w &&
                         hg->d_bn1_b && hg->d_bn2_w && hg->d_bn2_b, "eagcn_model_backward: null head gradient");
-    EAGCN_CHECK_ARG(layer_hi < m->n_layers && layer_lo >= 0 && layer_lo <= layer_hi + 1,
-                    "eagcn_model_backward_range: layers %d..%d of %d", layer_hi, layer_lo, m->n_layers);
-    EAGCN_CHECK_ARG(!with_head || layer_hi == m->n_layers - 1 || layer_hi < layer_lo,
-                    "eagcn_model_backward_range: the head's backward is followed by the top layer");
     ModelSaved sv;
     ModelScratch sc;
-    EAGCN_CHECK_ARG(carve_saved(saved, b, m, &sv) <= saved_bytes, "eagcn_model_backward: saved block too small");
-    EAGCN_CHECK_ARG(carve_scratch(scratch, b, m, &sc) <= scratch_bytes, "eagcn_model_backward: scratch too small");
+    ModelPlan mp;
+    RC(plan_backward(b, m, saved, saved_bytes, scratch, scratch_bytes, with_head, layer_hi, layer_lo, dx0 != nullptr, input_only, sv, sc, mp));
     const int F = m->head.f_in;
     // (no clearing launch: the forward call left the hand-off flags and the backward sums zero; owners reset their flags)
     const ZeroJob zb{nullptr, 0, sc.hsb, sc.n_hst};
@@ -729,7 +790,7 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
     const bool weighted = last->structure == EAGCN_STRUCT_WEIGHTED;
     const bool sampled = pad_sampled(m);
     if (with_head) {
-        const HeadPlan P = head_plan(b, m, sv, sc, nullptr, nullptr, dout, dgraph_rep, hg, size);
+        const HeadPlan P = head_plan(b, m, sv, sc, nullptr, nullptr, dout, dgraph_rep, hg, size, mp.top_formed);
         RC(head_backward_launches(m, P, stream));
         // (the gradient of the non-stored rows only enters the BatchNorm reductions, which the input-only form skips in eval mode)
         if (!(input_only && !m->training)) RC(readout_pad_backward(b, m, size, sv, sc, stream));
@@ -738,11 +799,6 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
     memset(&rgd, 0, sizeof(rgd));
     rgd.dg = sc.dg; rgd.F = F; rgd.size = size; rgd.mode = m->molfp_mode; rgd.map = make_colmap(&lay);
     const int top_l = m->n_layers - 1;
-    // a hidden Concate layer's dH and BatchNorm column sums come out of the dX product of the plane-pair layer above it, when both
-    // run in this call (layer.hip layer_hidden_sums_route; training, local BatchNorm): `fused` = the layer about to run
-    // finds them in its upstream buffer and in sc.hid_slab
-    BxBnEpi below;
-    bool fused = false;
     EdgeDrain pend_in, pend_out;
     pend_in.eacc = nullptr;
     pend_out.eacc = nullptr;                                     // (the input-only form hands no edge reduction down)
@@ -752,14 +808,7 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
         const int t = top_l - l;
         float* cur = (t & 1) ? sc.dxb : sc.dxa;
         float* other = (t & 1) ? sc.dxa : sc.dxb;
-        LayerSaved& L = sv.L[l];
-        eagcn_layer_bufs w;
-        memset(&w, 0, sizeof(w));
-        w.x = l == 0 ? sv.x0 : (hidden_planes_only(b, m, sv, l - 1) ? nullptr : sv.L[l - 1].xout);
-        w.P = L.P; w.Y = L.Y; w.rscale = L.rscale; w.bn = L.bn; w.xout = L.xout; w.pad_row = L.pad_row;
-        w.scratch = sc.layer; w.scratch_bytes = sc.layer_bytes; w.packed = L.packed; w.packed_bytes = L.packed_bytes;
-        w.stats_hook = m->stats_hook; w.stats_user = m->stats_user;
-        w.x_planes = l > 0 ? sv.L[l - 1].xout_planes : nullptr;
+        const LayerPlan& Q = mp.L[l];
         const bool top = l == top_l;
         const float* dpad = (weighted && top) ? sc.dpad : nullptr;
         // (a layer that has only its edge-gradient reduction left hands it to the next layer's first kernel -- if one follows in
@@ -768,24 +817,18 @@ static int model_backward_impl(const eagcn_batch* b, const eagcn_model* m, const
         o.rg = top ? &rgd : nullptr; o.dpad_views = top && sampled; o.zero_after = top ? &zb : nullptr;
         o.drain_in = pend_in.eacc ? &pend_in : nullptr; o.drain_out = (l > layer_lo && !input_only) ? &pend_out : nullptr;
         o.input_only = input_only;
-        if (top && !input_only && top_bn_sums(b, m)) {
+        // what the layers hand each other, as planned (plan_model): the read-out's sums to the top layer, dH and its sums from the dX
+        // product of the layer above -- the layer about to run finds them in its upstream buffer and in sc.hid_slab
+        if (Q.bwd.bn2 == BN2_STAGED_FROM_READOUT) {
             o.top_sums = sc.top_slab; o.top_nslab = top_bn_slabs(b->B);
-            o.top_dge = top_bn_gather_enabled() ? sc.top_dge : nullptr;
+            o.top_dge = Q.bwd.rows_late ? nullptr : sc.top_dge;
         }
-        if (fused) { o.dh_sums = sc.hid_slab; o.dh_nslab = hidden_bn_slabs(b->T); }
-        bool carried = false;
-        fused = l > layer_lo && !input_only && m->training && !m->stats_hook &&
-                layer_hidden_sums_route(b, &m->layer[l], &m->layer[l - 1], &below);
-        if (fused) {
-            below.Y = sv.L[l - 1].Y; below.bn = sv.L[l - 1].bn; below.row_m = b->row_m; below.slab = sc.hid_slab;
-            o.below = &below; o.below_done = &carried;
-        }
-        RC(layer_backward_impl(b, &m->layer[l], &w, top ? nullptr : cur, dpad, l > 0 ? other : dx0, input_only ? nullptr : &lg[l],
-                               stream, o));
+        if (Q.bwd.dh_given) { o.dh_sums = sc.hid_slab; o.dh_nslab = hidden_bn_slabs(b->T); }
+        if (Q.bwd.carries_below) o.below = &Q.below;
+        RC(layer_backward_impl(b, &m->layer[l], &Q.w, top ? nullptr : cur, dpad, l > 0 ? other : dx0, input_only ? nullptr : &lg[l],
+                               stream, Q.bwd, o));
         pend_in = pend_out;
         if (l == layer_lo) pend_in.eacc = nullptr;
-        fused = fused && carried;                                // (the layer's real plan decides: layer.hip bwd_products)
-        EAGCN_CHECK_ARG(!fused || !pend_in.eacc, "eagcn_model_backward: a plane-pair layer handed its edge reduction down");
     }
     return EAGCN_OK;
 }
@@ -798,6 +841,34 @@ extern "C" int eagcn_model_backward_range(const eagcn_batch* b, const eagcn_mode
     EAGCN_CHECK_GEMM3("eagcn_model_backward");
     return model_backward_impl(b, m, size, saved, saved_bytes, scratch, scratch_bytes, dout, dgraph_rep, lg, hg, with_head, layer_hi,
                                layer_lo, nullptr, false, stream);
+}
+
+extern "C" int eagcn_model_route(const eagcn_batch* b, const eagcn_model* m, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                                 int with_head, int layer_hi, int layer_lo, int has_dx0, int input_only, int32_t out[4][16]) {
+    RC(check_model(b, m, "eagcn_model_route"));
+    EAGCN_CHECK_ARG(saved && scratch && out, "eagcn_model_route: null argument");
+    ModelSaved sv;
+    ModelScratch sc;
+    ModelPlan P;
+    RC(plan_backward(b, m, saved, saved_bytes, scratch, scratch_bytes, with_head, layer_hi, layer_lo, has_dx0 != 0, input_only != 0, sv, sc, P));
+    memset(out, 0, sizeof(int32_t) * 4 * 16);
+    for (int l = 0; l < m->n_layers; ++l) {
+        const LayerPlan& Q = P.L[l];
+        const LayerRoute& f = Q.fwd;
+        const LayerRoute& r = Q.bwd;
+        const bool top = l == m->n_layers - 1, ran = l >= layer_lo && l <= layer_hi, used = r.bn2 == BN2_STAGED_FROM_READOUT;
+        int32_t* o = out[l];
+        o[0] = f.fwd_prod; o[1] = f.fwd_split_x; o[2] = f.fwd_agg; o[13] = l > 0 && !Q.w.x;
+        o[14] = (Q.planes_only ? 1 : 0) | (Q.skip_apply ? 2 : 0) | (top && P.top_formed ? 4 : 0);
+        if (!ran) continue;
+        const int32_t v[10] = {(int32_t)r.bwd_agg, (int32_t)r.bn2, r.rows_first, r.rows_late, r.store_dh, (int32_t)r.edge, r.edge_atomic, (int32_t)r.bwd_prod,
+                               r.bwd_split_x, r.defer_drain};
+        memcpy(o + 3, v, sizeof(v));
+        o[14] |= (used ? 8 : 0) | (used && !r.rows_late ? 16 : 0) | (r.dh_given ? 32 : 0) | (r.carries_below ? 64 : 0) | (r.dw_fused ? 128 : 0) |
+                 (r.bx_wide ? 256 : 0);
+        o[15] = r.dw_ny;
+    }
+    return EAGCN_OK;
 }
 
 // ---- d / d afm (eagcn_model_backward_input, attribution) -------------------------------------------------------------------------------

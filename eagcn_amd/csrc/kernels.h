@@ -300,26 +300,80 @@ struct LayerBwdOpts {
     // slabs [slab][fp][2] (HeadTopSums) -- the reduction pass over the rows is skipped and no dH is stored
     const double* top_sums = nullptr; int top_nslab = 0;
     const float* top_dge = nullptr;          // ... and dg / size per molecule [B][rg.F] (HeadTopSums.dge), or null: rows of rg are written
-    // model engine, a plane-pair layer above a Concate layer (layer_hidden_sums_route): the dX product's launch forms the layer BELOW's
-    // dH and its column sums in a tail pass (bx3.h BxBnEpi, complete but for C) ...
+    // model engine, a plane-pair layer above a Concate layer whose route carries the tail pass (LayerRoute.carries_below): the dX
+    // product's launch forms the layer BELOW's dH and its column sums (bx3.h BxBnEpi, complete but for C) ...
     const BxBnEpi* below = nullptr;
-    bool* below_done = nullptr;              // ... set when this call's dX product really carried it (the route is planned from the real buffers:
-                                             // a call whose products do not run as the plane pair ignores `below` and the layer below keeps its pass)
     // ... and that layer's call: dxout already holds dH, sum dH and sum dH xhat arrive as one fp64 slab [fp][2] per BX_EPI_ROWS packed
     // rows (dh_nslab: the slab CAPACITY; the finalize counts the written ones from the device-side row count) -- no reduction pass
     const double* dh_sums = nullptr; int dh_nslab = 0;
 };
-// would the backward of layer `up` (with d(input)) run its products as the plane pair, and that
-// of the Concate layer `low` below it store dH in a reduction pass and leave the second pass to lagg.hip -- the pass the dX units'
-// tail pass replaces (on the 128 x 128 kernel: bwd_products)?  Fills what of *ep is the layer's own (dropout, widths); the caller adds Y', the table, the mask and the slabs.
-bool layer_hidden_sums_route(const eagcn_batch* b, const eagcn_layer_params* up, const eagcn_layer_params* low, BxBnEpi* ep);
 inline int hidden_bn_slabs(int T) { return (T > 0 ? T + BX_EPI_ROWS - 1 : BX_EPI_ROWS) / BX_EPI_ROWS; }      // slab capacity for T packed rows
-// would the backward of top layer p (per-molecule upstream gradient) take the route that top_sums replaces a pass of?  (layer.hip)
-bool layer_top_sums_route(const eagcn_batch* b, const eagcn_layer_params* p);
 bool top_bn_sums_enabled();                  // eagcn_set_top_bn_sums != 0
 bool top_bn_gather_enabled();                // ... == 1: the staging gathers dg per molecule (2: rows of the read-out gradient are written)
+bool planes_only_enabled();                  // EAGCN_PLANES_ONLY: a hidden layer whose reader takes plane images alone leaves no fp32 output
+// a top layer's staging can gather the read-out gradient dge [B][F] per molecule: four adjacent exact columns with one 16-byte load
+bool top_gather_ok(const eagcn_layer_params* p, const float* dge, int F);
+
+// ---- the route of a layer call: which kernels it runs, decided ONCE by plan_layer (layer.hip) -- a pure host function of the batch
+// description, the layer, the buffers' addresses (alignment only), the ask and the switches.  The public entry points plan for
+// themselves, the model engine plans all layers of a call at once (head.hip plan_model); layer_forward_impl / layer_backward_impl carry
+// the route out, eagcn_layer_route / eagcn_model_route show it to the tests (the values are part of the C ABI: include/eagcn_hip.h)
+// REFUSED: x exists as plane images only and the plane products do not apply -- the call fails
+enum FwdProd { FWD_NONE = 0, FWD_PLANES, FWD_BALANCED, FWD_TILED, FWD_REFUSED };        // gemm_bx3.hip | gemm3.hip | gemm.hip
+enum AggPath { AGG_DENSE = 0, AGG_LAGG };                                 // matrix-core kernels of agg.hip | LDS-staged bond lists (lagg.hip)
+// where the BatchNorm backward's second pass dY' = sc (dH - c1 - xhat c2) happens
+enum Bn2 {
+    BN2_NONE = 0,
+    BN2_ELEMENTWISE,             // bn_bwd_apply_kernel on the dH the first pass stored (Concate: the upstream gradient is as wide as dH)
+    BN2_REDUCE_APPLY,            // bn_bwd_reduce_kernel again, dH re-formed (Weighted_sum: the upstream gradient is K times narrower:
+                                 // no write and read of T x Fp floats, HIV 9.74 -> 9.53 ms per step)
+    BN2_STAGED_FROM_DH,          // lagg.hip, while it stages the rows of the stored dH (it is the only consumer of dY')
+    BN2_STAGED_FROM_UPSTREAM,    // lagg.hip re-forms dH AND dY' from the layer's upstream gradient: neither exists in memory
+    BN2_STAGED_ROWMASK,          // ... of a Concate layer in eval mode (input-only form: dH = upstream x row mask x relu')
+    BN2_STAGED_FROM_READOUT      // ... of a Concate top layer in training mode whose column sums came from the read-out (LayerBwdOpts.top_sums):
+                                 // no reduction pass, no stored dH; lagg_top.hip re-forms dH from the read-out gradient, gathered per
+                                 // molecule (LayerBwdOpts.top_dge) or written out as rows first (rows_late)
+};
+enum EdgePath { EDGE_NONE = 0, EDGE_WITH_LAGG, EDGE_COLAUNCH };   // lagg.hip's gathers | one grid with agg.hip (3, an own launch: retired)
+enum BwdProd {
+    BWD_NONE = 0, BWD_PLANES_PAIR, BWD_PLANES_DW, BWD_PLANES_DX,      // gemm_bx3.hip: dX with dW | dW alone | dX alone (input-only)
+    BWD_G3_XK, BWD_G3_SCATTER,   // gemm3.hip pair: dW as one partial slab per XCD | written straight into the per-view gradients
+    BWD_TILED_PAIR, BWD_TILED_SEPARATE, BWD_TILED_DX,                 // gemm.hip: one grid | dW alone (no dX asked) | dX alone
+    BWD_REFUSED
+};
+struct PlanAsk {                 // (all false: a forward call)
+    bool has_dx = false;         // d(layer input) is asked for
+    bool mol_grad = false;       // the upstream gradient comes per molecule (ReadoutGrad)
+    bool input_only = false;
+    bool has_drain_out = false;  // a layer below could take this layer's edge-gradient reduction
+    bool top_sums = false;       // the BatchNorm backward's column sums are given (LayerBwdOpts.top_sums; the model engine alone asks)
+    bool top_gather = false;     // ... and the read-out gradient per molecule in a form the staging can gather (LayerBwdOpts.top_dge)
+    bool dh_given = false;       // the upstream buffer holds dH already and its column sums are given (LayerBwdOpts.dh_sums)
+    bool below = false;          // the layer below would take its dH and sums from this call's dX product (LayerBwdOpts.below)
+};
+struct LayerRoute {
+    FwdProd fwd_prod = FWD_NONE; bool fwd_split_x = false;      // split: the planes of x are produced here (launch_bx3_split)
+    AggPath fwd_agg = AGG_DENSE, bwd_agg = AGG_DENSE;
+    Bn2 bn2 = BN2_NONE;
+    bool rows_first = false, rows_late = false;                  // launch_readout_bwd_rows before the reduction | before the aggregation
+    bool store_dh = false;                                       // the first pass of the BatchNorm backward stores dH
+    EdgePath edge = EDGE_NONE; bool edge_atomic = false;         // atomic: the partials leave through the shared accumulators
+    BwdProd bwd_prod = BWD_NONE; bool bwd_split_x = false;
+    bool bx_wide = false;                                        // PLANES_PAIR / PLANES_DW: the launch runs on the 256 x 128 kernel (bx3_pick_wide)
+    // PlanAsk.below on PLANES_PAIR, 128 x 128 kernel: dX carries the tail pass that forms the layer below's dH and column sums (the 256 x
+    // 128 kernel does not: with it every launch of that kernel ran slower, DESIGN.md section 1 -- the layer below keeps its pass)
+    bool carries_below = false;
+    bool defer_drain = false;                                    // the edge reduction is left to the next layer's first kernel
+    bool dh_given = false;                                       // no reduction pass: dH and its sums came from the layer above's dX product
+    // a refinement below BWD_TILED_SEPARATE (first layer, no dX asked): dWcat leaves the transposed aggregation's epilogue as dw_ny
+    // slabs (lagg_dw.hip) -- no dP, no product launch; the slabs live in the dWcat area, or in the dP area this route leaves free
+    bool dw_fused = false; int dw_ny = 0; bool dw_in_dp = false;
+    bool bn2_staged() const { return bn2 >= BN2_STAGED_FROM_DH; }
+    bool bwd_planes() const { return bwd_prod >= BWD_PLANES_PAIR && bwd_prod <= BWD_PLANES_DX; }
+};
+LayerRoute plan_layer(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const PlanAsk& ask);
 int layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const float* dxout,
-                        const float* dpad_row, float* dx, const eagcn_layer_grads* g, void* stream,
+                        const float* dpad_row, float* dx, const eagcn_layer_grads* g, void* stream, const LayerRoute& r,
                         const LayerBwdOpts& o = LayerBwdOpts{});
 // model engine (head.hip): the backward of eagcn_model_backward_input with layer 0's d(input) left PACKED ([T][ld_in] inside the scratch
 // block, *dx0), and where the packed input lives inside `saved` (attr.hip)
@@ -334,12 +388,10 @@ int model_input_slot(const eagcn_batch* b, const eagcn_model* m, void* saved, si
 // unpacking; in eval mode no BatchNorm reduction either: dY' = sc dH is formed where the transposed aggregation stages its rows)
 // skip_apply: stop after the BatchNorm table (the caller applies it while it consumes Y: fused read-out of the top layer)
 // planes_only: the output leaves as the operand planes of the next layer's products ONLY (w->xout_planes; the fp32 matrix w->xout
-// is not written): the model engine asks for it when layer_reads_planes_only() holds for the layer above
-int layer_forward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, void* stream,
+// is not written): the model engine asks for it when the layer above, planned without an fp32 input, runs both directions from the
+// planes (head.hip plan_model); a layer that is handed w->x == nullptr fails loudly if it reaches a fallback
+int layer_forward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, void* stream, const LayerRoute& r,
                        bool prepacked, bool skip_apply = false, bool planes_only = false);
-// true when BOTH directions of layer p take their input x from its bf16 plane images and never from the fp32 matrix (the route
-// layer.hip plans for a call that brings the planes); a layer that is then handed w->x == nullptr fails loudly if it reaches a fallback
-bool layer_reads_planes_only(const eagcn_batch* b, const eagcn_layer_params* p);
 // eagcn_layer_bufs.aux_stream / eagcn_model.aux_stream are reserved (the backward runs on the call's one stream): a value is refused
 inline int check_reserved_null(const void* value, const char* who, const char* field) {
     EAGCN_CHECK_ARG(!value, "%s: %s is reserved and must be null", who, field);

@@ -989,63 +989,9 @@ static Fp32Products layer_fp32_products(const eagcn_batch* b, const LayerDims& d
     return q;
 }
 
-// ---- the route of a layer call -----------------------------------------------------------------------------------------------------
-// Which kernels a layer runs for a batch is decided ONCE per call, by plan_layer: a pure host function of the batch description,
-// the layer, the buffers' addresses (alignment only: nothing is dereferenced) and the switches below.  layer_forward_impl and
-// layer_backward_impl carry the route out; eagcn_layer_route shows it to the tests.  (The values are part of the C ABI:
-// include/eagcn_hip.h.)
-// REFUSED: x exists as plane images only and the plane products do not apply -- the call fails
-enum FwdProd { FWD_NONE = 0, FWD_PLANES, FWD_BALANCED, FWD_TILED, FWD_REFUSED };        // gemm_bx3.hip | gemm3.hip | gemm.hip
-enum AggPath { AGG_DENSE = 0, AGG_LAGG };                                 // matrix-core kernels of agg.hip | LDS-staged bond lists (lagg.hip)
-// where the BatchNorm backward's second pass dY' = sc (dH - c1 - xhat c2) happens
-enum Bn2 {
-    BN2_NONE = 0,
-    BN2_ELEMENTWISE,             // bn_bwd_apply_kernel on the dH the first pass stored (Concate: the upstream gradient is as wide as dH)
-    BN2_REDUCE_APPLY,            // bn_bwd_reduce_kernel again, dH re-formed (Weighted_sum: the upstream gradient is K times narrower:
-                                 // no write and read of T x Fp floats, HIV 9.74 -> 9.53 ms per step)
-    BN2_STAGED_FROM_DH,          // lagg.hip, while it stages the rows of the stored dH (it is the only consumer of dY')
-    BN2_STAGED_FROM_UPSTREAM,    // lagg.hip re-forms dH AND dY' from the layer's upstream gradient: neither exists in memory
-    BN2_STAGED_ROWMASK,          // ... of a Concate layer in eval mode (input-only form: dH = upstream x row mask x relu')
-    BN2_STAGED_FROM_READOUT      // ... of a Concate top layer in training mode whose column sums came from the read-out (LayerBwdOpts.top_sums):
-                                 // no reduction pass, no stored dH; lagg_top.hip re-forms dH from the read-out gradient, gathered per
-                                 // molecule (LayerBwdOpts.top_dge) or written out as rows first (rows_late)
-};
-enum EdgePath { EDGE_NONE = 0, EDGE_WITH_LAGG, EDGE_COLAUNCH };   // lagg.hip's gathers | one grid with agg.hip (3, an own launch: retired)
-enum BwdProd {
-    BWD_NONE = 0, BWD_PLANES_PAIR, BWD_PLANES_DW, BWD_PLANES_DX,      // gemm_bx3.hip: dX with dW | dW alone | dX alone (input-only)
-    BWD_G3_XK, BWD_G3_SCATTER,   // gemm3.hip pair: dW as one partial slab per XCD | written straight into the per-view gradients
-    BWD_TILED_PAIR, BWD_TILED_SEPARATE, BWD_TILED_DX,                 // gemm.hip: one grid | dW alone (no dX asked) | dX alone
-    BWD_REFUSED
-};
-struct PlanAsk {
-    bool has_dx;                 // d(layer input) is asked for
-    bool mol_grad;               // the upstream gradient comes per molecule (ReadoutGrad)
-    bool input_only;
-    bool has_drain_out;          // a layer below could take this layer's edge-gradient reduction
-    bool top_sums = false;       // the BatchNorm backward's column sums are given (LayerBwdOpts.top_sums; the model engine alone asks)
-    bool top_gather = false;     // ... and the read-out gradient per molecule in a form the staging can gather (LayerBwdOpts.top_dge)
-    bool dh_given = false;       // the upstream buffer holds dH already and its column sums are given (LayerBwdOpts.dh_sums)
-};
-struct LayerRoute {
-    FwdProd fwd_prod = FWD_NONE; bool fwd_split_x = false;      // split: the planes of x are produced here (launch_bx3_split)
-    AggPath fwd_agg = AGG_DENSE, bwd_agg = AGG_DENSE;
-    Bn2 bn2 = BN2_NONE;
-    bool rows_first = false, rows_late = false;                  // launch_readout_bwd_rows before the reduction | before the aggregation
-    bool store_dh = false;                                       // the first pass of the BatchNorm backward stores dH
-    EdgePath edge = EDGE_NONE; bool edge_atomic = false;         // atomic: the partials leave through the shared accumulators
-    BwdProd bwd_prod = BWD_NONE; bool bwd_split_x = false;
-    bool defer_drain = false;                                    // the edge reduction is left to the next layer's first kernel
-    bool dh_given = false;                                       // no reduction pass: dH and its sums came from the layer above's dX product
-    // a refinement below BWD_TILED_SEPARATE (first layer, no dX asked): dWcat leaves the transposed aggregation's epilogue as dw_ny
-    // slabs (lagg_dw.hip) -- no dP, no product launch; the slabs live in the dWcat area, or in the dP area this route leaves free
-    bool dw_fused = false; int dw_ny = 0; bool dw_in_dp = false;
-    bool bn2_staged() const { return bn2 >= BN2_STAGED_FROM_DH; }
-    bool bwd_planes() const { return bwd_prod >= BWD_PLANES_PAIR && bwd_prod <= BWD_PLANES_DX; }
-};
-
-// the switches (each read once).  EAGCN_AGG / EAGCN_LAGG_*: lagg.hip; EAGCN_GEMM_X6: gemm.hip; EAGCN_GEMM3_XK: gemm3.hip
+// ---- the route of a layer call (kernels.h LayerRoute): the switches (each read once).  EAGCN_AGG / EAGCN_LAGG_*: lagg.hip; EAGCN_GEMM_X6: gemm.hip; EAGCN_GEMM3_XK: gemm3.hip
 static bool sw_gemm3() { static const bool on = !env_flag("EAGCN_NO_GEMM3", false); return on; }
-static bool sw_planes_only() { static const bool on = env_flag("EAGCN_PLANES_ONLY", true); return on; }
+bool planes_only_enabled() { static const bool on = env_flag("EAGCN_PLANES_ONLY", true); return on; }
 // EAGCN_BWD_STORE_DH=1 / 0 forces the elementwise / the re-forming second pass (default: Bn2 above)
 static bool bn_bwd_two_pass(bool weighted) {
     static const int force = getenv("EAGCN_BWD_STORE_DH") ? (env_flag("EAGCN_BWD_STORE_DH", false) ? 1 : 0) : -1;
@@ -1063,9 +1009,12 @@ static int g_first_layer_fused = env_flag("EAGCN_FIRST_LAYER_FUSED", true) ? 1 :
 static long g_first_layer_fused_taken = 0;
 static int32_t g_first_layer_fused_last[3] = {0, 0, 0};      // of the last such call: slabs (= the grid's y extent), slabs in the dP area, uncapped y extent
 static bool first_layer_fused_enabled() { return g_first_layer_fused != 0; }
+// EAGCN_HIDDEN_BN_SUMS=0 in the environment / eagcn_set_hidden_bn_sums(0): the hidden layers' BatchNorm backward keeps its reduction pass
+static int g_hidden_bn_sums = env_flag("EAGCN_HIDDEN_BN_SUMS", true) ? 1 : 0;
+static long g_hidden_bn_taken = 0;
 
 static LayerRoute plan_layer(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const LayerDims& d,
-                             PlanAsk ask) {
+                             const PlanAsk& ask) {
     LayerRoute r;
     const bool wt = p->structure == EAGCN_STRUCT_WEIGHTED;
     bool general = false;                             // (code books: the edge reduction reads a view's whole histogram per channel)
@@ -1118,16 +1067,21 @@ static LayerRoute plan_layer(const eagcn_batch* b, const eagcn_layer_params* p, 
     }
 
     // dH and its sums were formed by the dX product of the layer above: the one route whose pass that replaces (dH stored by the
-    // pass, the second pass in lagg.hip's staging -- which then stages from the upstream buffer)
-    r.dh_given = ask.dh_given && r.bn2 == BN2_STAGED_FROM_DH && r.store_dh && !wt && !ask.mol_grad && !ask.input_only;
+    // pass, the second pass in lagg.hip's staging -- which then stages from the upstream buffer; a Concate layer in training mode,
+    // never more slabs than the pass writes)
+    r.dh_given = ask.dh_given && g_hidden_bn_sums && r.bn2 == BN2_STAGED_FROM_DH && r.store_dh && !wt && p->training && !ask.mol_grad &&
+                 !ask.input_only && hidden_bn_slabs(b->T) <= d.gxb;
     const bool planes = d.np && bx3_ok(bq.bw) && (!ask.has_dx || bx3_ok(bq.bx));
     r.bwd_split_x = planes && !w->x_planes && !ask.input_only;
     if (ask.input_only) r.bwd_prod = planes ? BWD_PLANES_DX : BWD_TILED_DX;
     else if (!planes && !w->x) r.bwd_prod = BWD_REFUSED;
     if (r.bwd_prod != BWD_NONE) return r;
     r.edge = (lagg && r.edge_atomic) ? EDGE_WITH_LAGG : EDGE_COLAUNCH;
-    if (planes) r.bwd_prod = ask.has_dx ? BWD_PLANES_PAIR : BWD_PLANES_DW;
-    else if (ask.has_dx && gemm3_layer(d.ld_in) && gemm3_ok(gq.gw) && gemm3_ok(gq.gx))
+    if (planes) {
+        r.bwd_prod = ask.has_dx ? BWD_PLANES_PAIR : BWD_PLANES_DW;
+        r.bx_wide = (ask.has_dx ? bx3_pick_wide(bq.bx, &bq.bw, b->t_hint) : bx3_pick_wide(bq.bw, nullptr, b->t_hint)) != 0;
+        r.carries_below = ask.below && ask.has_dx && !r.bx_wide;
+    } else if (ask.has_dx && gemm3_layer(d.ld_in) && gemm3_ok(gq.gw) && gemm3_ok(gq.gx))
         r.bwd_prod = gemm3_xk_enabled() ? BWD_G3_XK : BWD_G3_SCATTER;
     else r.bwd_prod = ask.has_dx ? BWD_TILED_PAIR : BWD_TILED_SEPARATE;
     // nothing but the edge reduction is left for this layer (no dW slabs to sum): the next layer's first backward kernel does it
@@ -1144,6 +1098,14 @@ static LayerRoute plan_layer(const eagcn_batch* b, const eagcn_layer_params* p, 
         r.dw_in_dp = r.dw_ny > cap_w;
     }
     return r;
+}
+LayerRoute plan_layer(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const PlanAsk& ask) {
+    return plan_layer(b, p, w, layer_dims(b, p), ask);
+}
+bool top_gather_ok(const eagcn_layer_params* p, const float* dge, int F) {
+    bool ok = dge && (reinterpret_cast<uintptr_t>(dge) & 15) == 0 && (F & 3) == 0;
+    for (int k = 0; k < p->K; ++k) ok = ok && (p->width[k] & 3) == 0;
+    return ok;
 }
 
 static int apply_launch(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const LayerDims& d,
@@ -1182,6 +1144,19 @@ extern "C" size_t eagcn_layer_bwd_scratch_bytes(const eagcn_batch* b, const eagc
     return carve_layer(nullptr, b, layer_dims(b, p), true, nullptr);
 }
 
+// both directions of layer p would take their input x from its bf16 plane images alone: the route of a hypothetical call that brings
+// them and nothing else (eagcn_layer_route out[13]; the model engine plans its real calls: head.hip plan_model)
+static bool layer_reads_planes_only(const eagcn_batch* b, const eagcn_layer_params* p) {
+    // (bx3_ok looks at alignment, strides and extents: the addresses stand for the 256-byte aligned pieces the executors carve)
+    void* const some = reinterpret_cast<void*>(static_cast<uintptr_t>(4096));
+    eagcn_layer_bufs w{};
+    w.x_planes = static_cast<const uint16_t*>(some); w.P = static_cast<float*>(some); w.scratch = some;
+    PlanAsk ask;
+    ask.has_dx = true;
+    const LayerRoute r = plan_layer(b, p, &w, ask);             // (no packed row: no product at all)
+    return planes_only_enabled() && r.fwd_prod == FWD_PLANES && r.bwd_prod == BWD_PLANES_PAIR;
+}
+
 extern "C" int eagcn_layer_route(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, int has_dx,
                                  int mol_grad, int input_only, int has_drain_out, int32_t out[16]) {
     int rc = check_layer(b, p, "eagcn_layer_route");
@@ -1189,7 +1164,9 @@ extern "C" int eagcn_layer_route(const eagcn_batch* b, const eagcn_layer_params*
     EAGCN_CHECK_ARG(w && out, "eagcn_layer_route: null argument");
     rc = check_reserved_null(w->aux_stream, "eagcn_layer_route", "eagcn_layer_bufs.aux_stream");
     if (rc) return rc;
-    const LayerRoute r = plan_layer(b, p, w, layer_dims(b, p), PlanAsk{has_dx != 0, mol_grad != 0, input_only != 0, has_drain_out != 0});
+    PlanAsk ask;
+    ask.has_dx = has_dx != 0; ask.mol_grad = mol_grad != 0; ask.input_only = input_only != 0; ask.has_drain_out = has_drain_out != 0;
+    const LayerRoute r = plan_layer(b, p, w, ask);
     const int32_t v[16] = {(int32_t)r.fwd_prod, r.fwd_split_x, (int32_t)r.fwd_agg, (int32_t)r.bwd_agg, (int32_t)r.bn2, r.rows_first, r.rows_late, r.store_dh, (int32_t)r.edge,
                            r.edge_atomic, (int32_t)r.bwd_prod, r.bwd_split_x, r.defer_drain,
                            layer_reads_planes_only(b, p), 0, 0};
@@ -1202,12 +1179,23 @@ static int clear_handoff_flags(const eagcn_layer_bufs* w, void* stream) {
     if (!(w && w->scratch && w->scratch_bytes >= gemm3_workspace_bytes())) return EAGCN_OK;
     return gemm3_clear_flags(w->scratch, w->scratch_bytes, (hipStream_t)stream);
 }
+// the public entry points plan for themselves, behind the checks plan_layer relies on
+static int plan_checked(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const PlanAsk& ask, const char* who,
+                        LayerRoute* r) {
+    const int rc = check_layer(b, p, who);
+    if (rc) return rc;
+    EAGCN_CHECK_ARG(w, "%s: null buffer", who);
+    *r = plan_layer(b, p, w, ask);
+    return EAGCN_OK;
+}
 extern "C" int eagcn_layer_forward(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w,
                                    void* stream) {
     EAGCN_CHECK_GEMM3("eagcn_layer_forward");
+    LayerRoute r;
     int rc = check_reserved_null(w ? w->aux_stream : nullptr, "eagcn_layer_forward", "eagcn_layer_bufs.aux_stream");
+    if (!rc) rc = plan_checked(b, p, w, PlanAsk{}, "eagcn_layer_forward", &r);
     if (!rc) rc = clear_handoff_flags(w, stream);
-    return rc ? rc : layer_forward_impl(b, p, w, stream, false);
+    return rc ? rc : layer_forward_impl(b, p, w, stream, r, false);
 }
 
 // parameters of up to four layers re-laid into their `packed` blocks by ONE launch (model engine)
@@ -1249,7 +1237,7 @@ int eagcn::pack_params_all(const eagcn_batch* b, const eagcn_layer_params* const
                                             else kernel<16><<<cdiv(d.fp, 16), 256, 0, s>>>(__VA_ARGS__); } while (0)
 
 int eagcn::layer_forward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w,
-                              void* stream, bool prepacked, bool skip_apply, bool planes_only) {
+                              void* stream, const LayerRoute& r, bool prepacked, bool skip_apply, bool planes_only) {
     hipStream_t s = (hipStream_t)stream;
     int rc = check_layer(b, p, "eagcn_layer_forward");
     if (rc) return rc;
@@ -1265,7 +1253,6 @@ int eagcn::layer_forward_impl(const eagcn_batch* b, const eagcn_layer_params* p,
     EAGCN_CHECK_ARG(!prepacked || w->packed, "eagcn_layer_forward: prepacked parameters need the packed block");
     if (!prepacked) launch_pack_params(pp, d, make_colmap(&p->in), sc.pk, s);
     EAGCN_LAUNCH_CHECK();
-    const LayerRoute r = plan_layer(b, p, w, d, PlanAsk{false, false, false, false});
     int nslab = 0, tiles_per_wg = agg_ksplit(b) ? 1 : 4;
     if (b->T > 0) {
         const double gemm_work = layer_gemm_work(b, p, d);
@@ -1324,18 +1311,6 @@ int eagcn::layer_forward_impl(const eagcn_batch* b, const eagcn_layer_params* p,
     return apply_launch(b, p, w, d, sc.pk.colp, s, planes_only);
 }
 
-// both directions of layer p would take their input x from its bf16 plane images alone: the route of a call that brings them
-bool eagcn::layer_reads_planes_only(const eagcn_batch* b, const eagcn_layer_params* p) {
-    if (!sw_planes_only() || !b || !p || b->T <= 0) return false;
-    // (bx3_ok looks at alignment, strides and extents: the addresses stand for the 256-byte aligned pieces the executors carve)
-    void* const some = reinterpret_cast<void*>(static_cast<uintptr_t>(4096));
-    eagcn_layer_bufs w;
-    memset(&w, 0, sizeof(w));
-    w.x_planes = static_cast<const uint16_t*>(some); w.P = static_cast<float*>(some); w.scratch = some;
-    const LayerRoute r = plan_layer(b, p, &w, layer_dims(b, p), PlanAsk{true, false, false, false});
-    return r.fwd_prod == FWD_PLANES && r.bwd_prod == BWD_PLANES_PAIR;
-}
-
 // EAGCN_TOP_BN_SUMS=0 in the environment / eagcn_set_top_bn_sums(0): the top layer's BatchNorm backward keeps its reduction pass
 static int g_top_bn_sums = !env_flag("EAGCN_TOP_BN_SUMS", true) ? 0 : env_int("EAGCN_TOP_BN_SUMS", 1) == 2 ? 2 : 1;
 bool eagcn::top_bn_sums_enabled() { return g_top_bn_sums != 0; }
@@ -1345,9 +1320,6 @@ extern "C" int eagcn_set_top_bn_sums(int on) {
     g_top_bn_sums = on == 2 ? 2 : on ? 1 : 0;
     return old;
 }
-// EAGCN_HIDDEN_BN_SUMS=0 in the environment / eagcn_set_hidden_bn_sums(0): the hidden layers' BatchNorm backward keeps its reduction pass
-static int g_hidden_bn_sums = env_flag("EAGCN_HIDDEN_BN_SUMS", true) ? 1 : 0;
-static long g_hidden_bn_taken = 0;
 /* layer backward calls (captured ones count when they are captured) that took dH and its sums from the layer above, since the last reset */
 extern "C" long eagcn_hidden_bn_sums_taken(int reset) {
     const long n = g_hidden_bn_taken;
@@ -1371,37 +1343,6 @@ extern "C" int eagcn_set_first_layer_fused(int on) {
     g_first_layer_fused = on ? 1 : 0;
     return old;
 }
-bool eagcn::layer_hidden_sums_route(const eagcn_batch* b, const eagcn_layer_params* up, const eagcn_layer_params* low, BxBnEpi* ep) {
-    if (!g_hidden_bn_sums || !b || !up || !low || b->T <= 0 || low->structure != EAGCN_STRUCT_CONCATE || !low->training) return false;
-    void* const some = reinterpret_cast<void*>(static_cast<uintptr_t>(4096));
-    eagcn_layer_bufs w;
-    memset(&w, 0, sizeof(w));
-    w.x_planes = static_cast<const uint16_t*>(some); w.x = static_cast<const float*>(some); w.P = static_cast<float*>(some); w.scratch = some;
-    const LayerDims du = layer_dims(b, up), dl = layer_dims(b, low);
-    if (du.ld_in != dl.fp || dl.ldo != dl.fp || hidden_bn_slabs(b->T) > dl.gxb) return false;      // (never more slabs than the pass writes)
-    const LayerRoute ru = plan_layer(b, up, &w, du, PlanAsk{true, false, false, false});
-    const LayerRoute rl = plan_layer(b, low, &w, dl, PlanAsk{true, false, false, false, false, false, true});
-    if (ru.bwd_prod != BWD_PLANES_PAIR || !rl.dh_given || rl.bwd_agg != AGG_LAGG) return false;
-    if (ep) {
-        memset(ep, 0, sizeof(*ep));
-        const DropArgs dr = drop_args(low->dropout, low->training != 0, low->seed, low->seed_dev);
-        ep->ldy = dl.fp; ep->fp = dl.fp;
-        ep->do_drop = dr.on; ep->thr = dr.thr; ep->inv_keep = dr.inv_keep; ep->seed = dr.seed; ep->seed_dev = dr.seed_dev;
-    }
-    return true;
-}
-// the backward of top layer p, given a per-molecule upstream gradient, would store dH in its reduction pass and leave the second pass
-// to lagg.hip: the one route whose reduction pass the read-out's sums replace (asked by the model engine before it forms them)
-bool eagcn::layer_top_sums_route(const eagcn_batch* b, const eagcn_layer_params* p) {
-    if (!b || !p || b->T <= 0 || p->structure != EAGCN_STRUCT_CONCATE || !p->training) return false;
-    void* const some = reinterpret_cast<void*>(static_cast<uintptr_t>(4096));
-    eagcn_layer_bufs w;
-    memset(&w, 0, sizeof(w));
-    w.x_planes = static_cast<const uint16_t*>(some); w.x = static_cast<const float*>(some); w.P = static_cast<float*>(some); w.scratch = some;
-    const LayerRoute r = plan_layer(b, p, &w, layer_dims(b, p), PlanAsk{true, true, false, false, true});
-    return r.bn2 == BN2_STAGED_FROM_READOUT && r.bwd_agg == AGG_LAGG && r.edge == EDGE_WITH_LAGG;
-}
-
 int eagcn::layer_apply_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, void* stream) {
     EAGCN_CHECK_ARG(b && p && w && w->bn && w->xout && w->pad_row && w->packed, "layer_apply: null buffer");
     const LayerDims d = layer_dims(b, p);
@@ -1425,9 +1366,13 @@ extern "C" int eagcn_layer_backward(const eagcn_batch* b, const eagcn_layer_para
                                     const float* dxout, const float* dpad_row, float* dx,
                                     const eagcn_layer_grads* g, void* stream) {
     EAGCN_CHECK_GEMM3("eagcn_layer_backward");
+    LayerRoute r;
     int rc = check_reserved_null(w ? w->aux_stream : nullptr, "eagcn_layer_backward", "eagcn_layer_bufs.aux_stream");
+    PlanAsk ask;
+    ask.has_dx = dx != nullptr;
+    if (!rc) rc = plan_checked(b, p, w, ask, "eagcn_layer_backward", &r);
     if (!rc) rc = clear_handoff_flags(w, stream);
-    return rc ? rc : layer_backward_impl(b, p, w, dxout, dpad_row, dx, g, stream);
+    return rc ? rc : layer_backward_impl(b, p, w, dxout, dpad_row, dx, g, stream, r);
 }
 
 namespace {
@@ -1440,8 +1385,8 @@ struct LayerBwd {
     bool wt, dg; DropArgs drop; double gemm_work;
     int nsplit = 0, xk_G = 0;
     bool bx_slabs = false;       // dWcat holds the k-chunk slabs of the plane GEMM (all of them written)
-    int bx_per = 0;              // > 0: that product shared its launch with dX (workgroups per XCD: bx3.h bx3_used_splits)
-    int bx_wide = 0;             // ... and which of the two plane-GEMM kernels wrote the slabs (the chunk policy counts ITS tiles)
+    int bx_per = 0;              // > 0: that product shared its launch with dX (workgroups per XCD: bx3.h bx3_used_splits; the chunk policy
+                                 // counts the tiles of the kernel that wrote the slabs: r.bx_wide)
 };
 }  // namespace
 
@@ -1603,29 +1548,23 @@ static int bwd_products(LayerBwd& c, const LayerOperands& o) {
     case BWD_PLANES_DX: return launch_bx3(bq.bx, nullptr, d.np, s, c.gemm_work, PROF_GEMM, bx3_pick_wide(bq.bx, nullptr, b->t_hint));
     case BWD_TILED_DX: return launch_gemm(gq.gx, s);
     case BWD_PLANES_PAIR: {
-        c.bx_wide = bx3_pick_wide(bq.bx, &bq.bw, b->t_hint);
         BxProb bx = bq.bx;
-        // the layer below's dH and column sums leave with dX (bx3.h BxBnEpi) -- on the 128 x 128 kernel: the 256 x 128 kernel does not
-        // carry the tail pass (with it every launch of that kernel, this route or not, ran slower: DESIGN.md section 1), its launches
-        // leave the layer below on its reduction pass
-        if (c.o.below && !c.bx_wide) {
+        if (c.r.carries_below) {       // the layer below's dH and column sums leave with dX (bx3.h BxBnEpi)
             EAGCN_CHECK_ARG(c.o.below->Y && c.o.below->bn && c.o.below->row_m && c.o.below->slab && c.o.below->fp == bx.N && bx.ldc == bx.N,
                             "eagcn_layer_backward: incomplete description of the layer below");
             // (bx3_epi.h: a lane takes four adjacent columns of dX and Y' at once -- inside or outside the matrix together)
             EAGCN_CHECK_ARG((bx.N & 3) == 0 && (c.o.below->ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(c.o.below->slab) & 15) == 0,
                             "eagcn_layer_backward: the tail pass of the dX product needs packed widths that are multiples of 4");
             bx.ep = *c.o.below;
-            if (c.o.below_done) *c.o.below_done = true;
         }
-        rc = launch_bx3(bx, &bq.bw, d.np, s, 2.0 * c.gemm_work, PROF_GEMM_PAIR, c.bx_wide);
+        rc = launch_bx3(bx, &bq.bw, d.np, s, 2.0 * c.gemm_work, PROF_GEMM_PAIR, c.r.bx_wide);
         c.nsplit = d.bx_splits;                       // partial slabs of dWcat: summed and scattered by unpack_grads
         c.bx_slabs = true;
         c.bx_per = bx3_pair_policy() ? std::max(1, bx3_grid() >> 3) : 0;
         return rc;
     }
     case BWD_PLANES_DW:
-        c.bx_wide = bx3_pick_wide(bq.bw, nullptr, b->t_hint);
-        rc = launch_bx3(bq.bw, nullptr, d.np, s, c.gemm_work, PROF_GEMM, c.bx_wide);
+        rc = launch_bx3(bq.bw, nullptr, d.np, s, c.gemm_work, PROF_GEMM, c.r.bx_wide);
         c.nsplit = d.bx_splits;
         c.bx_slabs = true;
         return rc;
@@ -1668,7 +1607,7 @@ static int bwd_unpack(LayerBwd& c) {
                                                                                   (c.r.dw_fused && c.r.dw_in_dp) ? sc.dP : sc.dWcat,
                                                                                   c.bx_slabs ? -c.nsplit : c.nsplit, d.wslab,
                                                                                   shared ? sc.eacc : sc.datt, nedge, sc.pk.rsig,
-                                                                                  wblocks, b->meta, c.xk_G, shared ? 1 : 0, c.bx_per, c.bx_wide,
+                                                                                  wblocks, b->meta, c.xk_G, shared ? 1 : 0, c.bx_per, c.r.bx_wide ? 1 : 0,
                                                                                   c.r.dw_fused ? 1 : 0);        // (the aggregation's epilogue wrote every one of its slabs, whatever the row count)
     EAGCN_LAUNCH_CHECK();
     return EAGCN_OK;
@@ -1676,7 +1615,7 @@ static int bwd_unpack(LayerBwd& c) {
 
 int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w,
                                const float* dxout, const float* dpad_row, float* dx, const eagcn_layer_grads* g, void* stream,
-                               const LayerBwdOpts& o) {
+                               const LayerRoute& r, const LayerBwdOpts& o) {
     if (o.drain_out) o.drain_out->eacc = nullptr;
     int rc = check_layer(b, p, "eagcn_layer_backward");
     if (rc) return rc;
@@ -1708,25 +1647,17 @@ int eagcn::layer_backward_impl(const eagcn_batch* b, const eagcn_layer_params* p
     EAGCN_LAUNCH_CHECK();
     EAGCN_CHECK_ARG(!o.top_sums || (o.top_nslab >= 1 && c.dg && !o.input_only && !o.drain_in && p->training && !w->stats_hook),
                     "eagcn_layer_backward: column sums from the read-out belong to a top layer in training mode with a local BatchNorm");
-    // the staging gathers four adjacent exact columns of a molecule's gradient with one 16-byte load
-    bool gather = o.top_sums && o.top_dge && (reinterpret_cast<uintptr_t>(o.top_dge) & 15) == 0 && o.rg && (o.rg->F & 3) == 0;
-    for (int k = 0; k < p->K; ++k) gather = gather && (p->width[k] & 3) == 0;
     EAGCN_CHECK_ARG(!o.dh_sums || (o.dh_nslab >= hidden_bn_slabs(b->T) && dxout && !c.dg && !o.input_only && !o.drain_in && !o.zero_after &&
                                    !dpad_row && p->training && !w->stats_hook && !o.top_sums),
                     "eagcn_layer_backward: dH and its column sums from the layer above belong to a hidden layer in training mode with a local BatchNorm");
-    c.r = plan_layer(b, p, w, d, PlanAsk{dx != nullptr, c.dg, o.input_only, o.drain_out != nullptr, o.top_sums != nullptr, gather, o.dh_sums != nullptr});
-    if (o.below_done) *o.below_done = false;
-    // (a layer whose products do not run as the plane pair after all ignores o.below: the layer below keeps its pass.  dH in place of
-    //  the upstream gradient cannot be undone -- but whether THIS layer takes it depends on the batch description, the structure and
-    //  the switches alone, none of which the prediction of layer_hidden_sums_route saw differently)
-    if (o.dh_sums && !c.r.dh_given) {
-        set_error("eagcn_layer_backward: dH and its column sums were given, but the layer's route has no use for them");
-        return EAGCN_ERR_ARG;
-    }
-    if (o.top_sums && c.r.bn2 != BN2_STAGED_FROM_READOUT) {
-        set_error("eagcn_layer_backward: column sums from the read-out were given, but the layer's route has no use for them");
-        return EAGCN_ERR_ARG;
-    }
+    c.r = r;
+    // options and a route that do not belong together (the model engine derives both from one plan)
+    EAGCN_CHECK_ARG(!o.dh_sums || r.dh_given, "eagcn_layer_backward: dH and its column sums were given, but the layer's route has no use for them");
+    EAGCN_CHECK_ARG(!o.top_sums || r.bn2 == BN2_STAGED_FROM_READOUT,
+                    "eagcn_layer_backward: column sums from the read-out were given, but the layer's route has no use for them");
+    EAGCN_CHECK_ARG((!r.dh_given || o.dh_sums) && (!r.carries_below || o.below) &&
+                        (r.bn2 != BN2_STAGED_FROM_READOUT || (o.top_sums && (r.rows_late || top_gather_ok(p, o.top_dge, o.rg->F)))),
+                    "eagcn_layer_backward: the route was planned for other arguments");
 
     rc = bwd_batchnorm(c);
     if (rc) return rc;

@@ -464,6 +464,22 @@ int eagcn_model_backward_range(const eagcn_batch* b, const eagcn_model* m, const
                                size_t saved_bytes, void* scratch, size_t scratch_bytes, const float* dout,
                                const float* dgraph_rep, const eagcn_layer_grads* lg, const eagcn_head_grads* hg,
                                int with_head, int layer_hi, int layer_lo, void* stream);
+/* The plan of one engine call, for tests and tools: what the library decides ONCE per eagcn_model_forward* / eagcn_model_backward* call,
+ * from the buffers the call runs on, and then carries out.  A pure host function as eagcn_layer_route -- `saved` / `scratch` are only
+ * carved (sizes are checked), nothing is dereferenced or launched.  The ask is that of eagcn_model_backward_range, with has_dx0:
+ * layer 0 forms d(its input) and input_only: no parameter gradient (both: eagcn_model_backward_input); layer_hi < layer_lo asks for
+ * no layer's backward -- the plan of a forward call.
+ *   out[l][0..13]  as eagcn_layer_route, of the calls the engine makes for layer l: the forward's out[0..2] for every layer, the
+ *                  backward's out[3..12] for the layers in [layer_lo, layer_hi] (0 elsewhere); out[l][13] = the layer is handed no fp32
+ *                  input (the layer below wrote plane images only)
+ *   out[l][14]     bits: 1 the output leaves as plane images only | 2 the apply pass is skipped (fused read-out) | 4 the top layer's
+ *                  BatchNorm column sums are formed by the read-out and the head's backward | 8 the top layer uses them | 16 ... and
+ *                  gathers the read-out gradient per molecule | 32 dH and its column sums are given by the layer above | 64 this layer's
+ *                  dX product carries the tail pass that forms them for the layer below | 128 dW leaves the aggregation's epilogue |
+ *                  256 the plane pair / dW launch runs on the 256 x 128 kernel.  Bits 1, 2, 4 do not depend on the ask
+ *   out[l][15]     slabs of that epilogue (dw_ny) */
+int eagcn_model_route(const eagcn_batch* b, const eagcn_model* m, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                      int with_head, int layer_hi, int layer_lo, int has_dx0, int input_only, int32_t out[4][16]);
 
 /* ---- d / d afm: the gradient of a prediction with respect to the atom features ("which atoms drive this prediction") ----------------
  * d(out.dout + graph_rep.dgraph_rep) / d afm, dense [B][N][n_afeat] (the row stride eagcn_model_pack_input reads): every entry written

@@ -148,7 +148,7 @@ def check_invariants(r, training, input_only, x_planes, has_dx, what):
         assert input_only and not training, what
     plane_routes = r[FWD_PROD] == FWD_PLANES and r[BWD_PROD] in (PLANES_PAIR, PLANES_DW, PLANES_DX)
     assert (r[FWD_SPLIT] or r[BWD_SPLIT]) <= (not x_planes), what           # planes that were brought are never formed again
-    if x_planes and has_dx:              # the question layer_reads_planes_only answers, asked of a call that brings the planes
+    if x_planes and has_dx:              # the question out[13] answers, asked of a call that brings the planes
         assert bool(r[PLANES_ONLY]) == (plane_routes and not r[FWD_SPLIT] and not r[BWD_SPLIT]), what
     elif r[PLANES_ONLY]:
         assert r[FWD_PROD] == FWD_PLANES, what

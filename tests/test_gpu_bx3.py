@@ -241,7 +241,7 @@ torch.save({'out': out.detach().cpu(), 'g': {k: p.grad.cpu() for k, p in m.named
 
 def test_hidden_layers_without_fp32_twin_are_bit_identical():
     """Round 6: where the layer above reads its input from the plane images in both directions, a hidden layer stores no fp32 output
-    (csrc/layer.hip layer_reads_planes_only, bn_apply).  EAGCN_PLANES_ONLY=0 keeps the fp32 twin: the same arithmetic either way, so
+    (csrc/head.hip plan_model, csrc/layer.hip bn_apply).  EAGCN_PLANES_ONLY=0 keeps the fp32 twin: the same arithmetic either way, so
     outputs and every gradient must be BIT-identical -- eager engine and captured step, three layers (two hidden outputs), widths
     that take the plane path (>= 128 columns) and, as the control, widths that do not (the switch then changes nothing at all).
     Subprocesses: the switch is read once per process."""

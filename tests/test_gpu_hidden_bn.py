@@ -258,6 +258,70 @@ def test_fewer_rows_than_one_block_five_views(n_layers):
     _check('tiny5', _tiny_wide_batch(), WIDE, n_layers, 0.0, False)
 
 
+NARROW = dict(chans=[6, 4], w1=[64, 64], w2=[64, 64])       # Fp = 128: the narrowest layer whose output leaves as plane images
+
+
+@pytest.mark.parametrize('wide', [False, True], ids=['by_size', 'wide_kernel'])
+def test_engine_runs_the_plan_it_reports(wide, monkeypatch):
+    """The hand-offs a backward call takes are the ones its plan reports (eagcn_model_route, asked with the very blocks the call runs
+    on): three Concate layers of two 64-column views, six chain molecules of 3..20 atoms, one eager training step.  The layer calls
+    that found dH and its sums in their upstream buffer (eagcn_hidden_bn_sums_taken) and those whose weight gradient left the
+    aggregation's epilogue (eagcn_first_layer_fused_taken) are as many as the plan has layers with bit 32 and bit 128 -- by default
+    both hidden links and the first layer, none of the links once every plane GEMM is forced onto the 256 x 128 kernel, which does
+    not carry the tail pass.  The gradients hold the file's bounds against the oracle either way."""
+    import ctypes as C
+    from eagcn_amd import EAGCN, _lib
+    from eagcn_amd.losses import fused_classification_loss
+    lib = _lib.load()
+    sizes = [3, 20, 7, 12, 5, 16]
+    mb = _mol_batch(sizes, [_chain(0, n - 1) for n in sizes], 20, 13, NARROW['chans'])
+    p, n_layers = 0.3, 3
+    torch.manual_seed(77)
+    hseed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    orc = _oracle('narrow', mb, NARROW, n_layers, p, hseed)
+    plans = []
+    backward = lib.eagcn_model_backward
+
+    def planned_backward(b, m, size, saved, saved_bytes, scratch, scratch_bytes, *rest):
+        out = (C.c_int32 * 16 * 4)()
+        _lib.check(lib.eagcn_model_route(b, m, saved, saved_bytes, scratch, scratch_bytes, 1, n_layers - 1, 0, 0, 0, C.byref(out)), 'eagcn_model_route')
+        plans.append([list(row) for row in out])
+        return backward(b, m, size, saved, saved_bytes, scratch, scratch_bytes, *rest)
+    monkeypatch.setattr(lib, 'eagcn_model_backward', planned_backward)
+    old = lib.eagcn_set_bx3_wide(1) if wide else None
+    try:
+        dev = torch.device('cuda', 0)
+        hip = EAGCN(NARROW['chans'][0], 24, n_den1=N_DEN1, n_den2=N_DEN2, nclass=NCLASS, dropout=p, structure='Concate', molfp_mode='sum',
+                    n_layers=n_layers, widths1=NARROW['w1'], widths2=NARROW['w2'], rel_channels=NARROW['chans'], grad_mode='direct',
+                    graph=False, validate='deferred').to(dev).train()
+        hip.load_state_dict(orc['sd'], strict=True)
+        dense = tuple(t.to(dev) for t in mb.dense())
+        labels = torch.from_numpy(mb.labels).to(dev)
+        bw = torch.tensor(bce_weights(NCLASS), dtype=torch.float32, device=dev)
+        lib.eagcn_hidden_bn_sums_taken(1)
+        lib.eagcn_first_layer_fused_taken(1)
+        torch.manual_seed(77)
+        out, _, gr = hip(*dense)
+        fused_classification_loss(out, labels, bw).backward()
+        torch.cuda.synchronize()
+        taken = (lib.eagcn_hidden_bn_sums_taken(1), lib.eagcn_first_layer_fused_taken(1))
+    finally:
+        if wide:
+            lib.eagcn_set_bx3_wide(old)
+    assert len(plans) == 1, len(plans)
+    bits = [row[14] for row in plans[0][:n_layers]]
+    print('plan bits per layer: %s, taken (hidden sums, first-layer dW): %s' % (bits, taken))
+    assert taken == (sum(bool(v & 32) for v in bits), sum(bool(v & 128) for v in bits)), (taken, bits)
+    assert [bool(v & 32) for v in bits] == ([False] * 3 if wide else [True, True, False]), bits
+    assert [bool(v & 256) for v in bits] == [False, wide, wide] and [bool(v & 64) for v in bits] == [False, not wide, not wide], bits
+    grads = {k: q.grad.detach().clone() for k, q in hip.named_parameters() if q.grad is not None}
+    g32, g64 = orc['g32'], orc['g64']
+    assert set(grads) == set(g32)
+    scale = max(v.abs().max().item() for v in g32.values())
+    for k in sorted(grads):
+        assert_grad_parity(grads[k], g32[k], lambda k=k: g64[k], scale, '%s narrow/%s' % (k, 'wide' if wide else 'by_size'))
+
+
 def test_tile_edges_on_the_wide_kernel():
     """The 256 x 128 kernel does not carry the tail pass: its launches leave the layer below on the reduction pass.  The library reads
     EAGCN_BX3_WIDE once: a child process runs the three-layer dropout case of test_tile_edges with it set -- _check asserts there that

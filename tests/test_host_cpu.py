@@ -373,6 +373,22 @@ def test_layer_routes_by_batch_layer_and_call(switches):
     assert r.returncode == 0 and 'routes checked: 336, refusals checked: 336' in r.stdout, r.stdout + r.stderr
 
 
+@pytest.mark.parametrize('switches', [{}, {'EAGCN_BX3_WIDE': '0'}, {'EAGCN_BX3_WIDE': '1'}, {'EAGCN_GEMM_X6': '0'}],
+                         ids=lambda s: ','.join('%s=%s' % kv for kv in s.items()) or 'default')
+def test_model_plans_by_model_batch_and_call(switches):
+    """eagcn_model_route (csrc/head.hip plan_model: what every layer of an engine call is handed and runs and what the layers hand
+    each other, decided once per call from the call's buffers) against the plans written out in tests/model_route_check.py: eleven
+    models and batches x the forward, the whole backward with and without the head, with d(input), input-only and both halves of
+    the data-parallel split x the setters of the three fused hand-offs, and the invariants that tie the layers of a plan together.
+    In a subprocess: the library reads its switches once."""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if not k.startswith('EAGCN_')}
+    env.update(switches)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'model_route_check.py')], capture_output=True, text=True, cwd=str(ROOT), env=env)
+    assert r.returncode == 0 and 'model plans checked: 405' in r.stdout, r.stdout + r.stderr
+
+
 def test_bond_list_buffers_are_laid_out_without_overlap():
     """_lib.set_bond_lists: row / column list headers, per-molecule records and the row-block records (two int4 per block, at most one
     block per molecule, 16-byte aligned) inside ONE int32 buffer of bond_ptrs_len(T, B) words; list entries with their 64-bit codes
