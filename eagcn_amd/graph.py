@@ -17,6 +17,15 @@ of batch k+1 -- index kernels, packing of ``afms``, seed upload -- runs on a sid
 still executing the backward of batch k; it only has to wait for the backward of batch k-1, the previous
 user of its slot.  The main stream then sees nothing but graph launches and the caller's loss.
 The captured backward writes the parameter gradients straight into the buffer ``p.grad`` are views of.
+
+The pieces, each written once:
+  * ``FlagHandoff`` / ``EventHandoff``: everything that orders the side stream against the step, in its two forms;
+  * ``BatchRing``: what the host keeps per batch in flight (pinned validity words, their event, pinned seed staging) and the
+    one place that turns it into an error; ``raise_sticky`` for the two sticky words of the library;
+  * ``grads_before`` / ``grads_attach``: a step's gradients attached as ``loss.backward()`` would;
+  * ``GraphRunner._run``: the one capture site ("first use of a place runs eagerly and is captured, later uses replay") behind
+    ``forward``, ``train_step`` and ``attributions``.
+graph_composed.ComposedRunner shares the ring and the gradient helper.
 """
 import ctypes as C
 import os
@@ -28,26 +37,6 @@ from . import ops
 from .ops import _index_stream, _ptr, _stream
 
 _RING = 4
-# hold the side-stream batch work until the previous step's FORWARD graph has finished: it then runs beside the loss and
-# the head / BatchNorm backward (latency chains on a few CUs) instead of beside the layer products (measured round 2:
-# 0.5228 -> 0.5175 ms/step at B=256, 1.2386 -> 1.2162 at B=1024; the wave-per-SIMD GEMM is sensitive to co-runners)
-_SIDE_AFTER_FWD = os.environ.get('EAGCN_SIDE_AFTER_FWD', '1') == '1'
-# EAGCN_SIDE_PLACED=1 (opt-in, measured SLOWER): one captured graph per step has no launch boundary behind the forward to hang an
-# event on, so the forward itself bumps a device word behind the read-out (eagcn_model.fwd_signal) and the side stream parks one
-# polling wavefront until the previous step has got there (eagcn_stream_wait_counter): the next batch's index scan then runs under
-# the head / loss / head-backward kernels instead of beside the persistent plane GEMMs (which it stretches from 150 to 189 us at
-# B = 1024, while the one-workgroup `index_offsets` waits 113 us for a CU: profiles/r04_b1024_step_timeline.txt).  Result (round 4,
-# two runs each): B = 1024 0.936 -> 0.970 ms, HIV 8.10 -> 8.86, C5 15.97 -> 17.38, Lipo 1.434 -> 1.465, B = 256 unchanged -- the
-# index build is 0.14-2.4 ms of side-stream work that needs the WHOLE previous step to hide in; holding it back until that step's
-# forward is over puts its tail on the critical path.  Being slowed down by co-runners is cheaper than not overlapping.
-# Round 6 (batch hand-off through device flags, the index build's clears in one launch): the placed form wins where the index chain
-# FITS under the head: configs[1] 0.378 -> 0.372 ms (the chain no longer meets the forward plane GEMM, which needs empty CUs), and
-# still loses where it does not (B = 1024: 0.829 -> 0.870).  `auto` = by the padded rows of the batch.
-# Measured again at the end of round 6 (shorter aggregation launches, the signal raised by the head's first launch), same-box A/B on two
-# boxes, tools/r6_env_ab.sh: configs[1] 0.374 -> 0.361 and 0.388 -> 0.376 ms WITHOUT the placement -- the unplaced index build again
-# hides under the whole step.  Default: off (EAGCN_SIDE_PLACED=0 | auto | 1).
-_SIDE_PLACED = os.environ.get('EAGCN_SIDE_PLACED', '0')
-_SIDE_PLACED_MAX_ROWS = int(os.environ.get('EAGCN_SIDE_PLACED_MAX_ROWS', '40000'))
 # a data-parallel step whose gradient all-reduce cannot be captured into the step graph is an ERROR instead of a (warned)
 # fallback to a host-issued collective: bench.py --require-in-graph-allreduce, tools/run_scale.sh
 _REQUIRE_IN_GRAPH = os.environ.get('EAGCN_REQUIRE_IN_GRAPH_ALLREDUCE', '0') == '1'
@@ -101,6 +90,205 @@ def _drain_collectives(device):
     if dist.is_available() and dist.is_initialized() and _CAPTURE_DRAIN_S > 0:
         import time
         time.sleep(_CAPTURE_DRAIN_S)
+
+
+class EventHandoff:
+    """What orders the side stream (a batch's preparation) against the main stream (the steps), through stream events; also the
+    base of the flag form.  A runner calls, per step: begin() in front of the preparation, ready() behind it, started() once per
+    executed forward, forward_done() / step_done() behind it, reset() when a step failed; wire() once per Model struct.  Streams
+    and events are only used through wait_event / record / cuda_stream, `new_event` makes an event: a CPU test drives it with fakes.
+
+    Event form: every begin() records an event on the main stream -- its position is "the previous step is done" -- and with
+    `overlap` the side stream waits for the event of the begin() BEFORE, behind which the step before the previous one, the last
+    user of this batch's slot, is done.  ready() with `overlap` orders the main stream behind an event recorded on the side
+    stream; without `overlap` the preparation ran on the main stream and nothing more is recorded or waited for."""
+
+    def __init__(self, new_event):
+        self.new_event = new_event
+        self.starts = 0                # forwards executed so far (S)
+        self.prev = None               # main-stream event of the last begin()
+        self.fwd_done = None           # main-stream position behind the last unfused forward graph
+
+    def wire(self, model, slot=None):
+        """The hand-off words of `slot` into a Model struct (none: `slot` None, or this form)."""
+        model.wait_flag = model.start_signal = None
+
+    def _slot_free(self, main, side, overlap):
+        free, self.prev = self.prev, self.new_event()
+        self.prev.record(main)
+        if overlap and free is not None:
+            side.wait_event(free)
+
+    def begin(self, main, side, overlap):
+        """In front of a batch's preparation on `side` (= `main` without `overlap`): the slot's last user is done, and the work is
+        held back until the FORWARD of the previous unfused step has finished -- from there on the main stream runs the caller's
+        loss and the head's backward, short kernels on a few CUs under which the HBM-streaming index scan costs nothing (round 2:
+        0.5228 -> 0.5175 ms/step at B = 256, 1.2386 -> 1.2162 at B = 1024 against a start beside the layer GEMMs)."""
+        self._slot_free(main, side, overlap)
+        if overlap and self.fwd_done is not None:
+            side.wait_event(self.fwd_done)
+
+    def ready(self, slot, main, side, overlap):
+        """Behind the batch's last preparatory work (torch's copies included) on `side`: the step may consume the slot."""
+        if overlap:
+            done = self.new_event()
+            done.record(side)
+            main.wait_event(done)
+
+    def started(self):
+        """One executed forward (eager, or a replay of a graph that holds one hand-off-carrying forward)."""
+        self.starts += 1
+
+    def forward_done(self, main):
+        self.fwd_done = self.new_event()
+        self.fwd_done.record(main)
+
+    def step_done(self):
+        """A fused step has no launch boundary behind its forward: the next preparation only waits for its slot."""
+        self.fwd_done = None
+
+    def reset(self):
+        """A step failed between its batch-ready signal and the launch that consumes it (nothing to undo with events)."""
+
+
+class FlagHandoff(EventHandoff):
+    """Flag form.  Per slot a device word "this slot's batch is prepared" (`ready` + 4 * slot), set behind the batch's last
+    preparatory kernel (eagcn_stream_signal_flag) and polled and cleared by the step's first launch (eagcn_model.wait_flag).  The
+    other direction: every forward adds 1 to the word at `start` in its first launch (eagcn_model.start_signal); when the S-th
+    forward issued on the main stream has STARTED, everything issued before it -- the steps that used the slots last -- is done, so
+    from S = 2 on the side stream waits for that count (eagcn_stream_wait_counter) instead of for an event recorded on the main
+    stream between two step graphs.  `words` reaches the two device words for reset(): synchronize(), zero_ready(), set_start(v)."""
+
+    def __init__(self, new_event, lib, ready, start, words):
+        EventHandoff.__init__(self, new_event)
+        self.lib, self.ready_word, self.start_word, self.words = lib, int(ready), int(start), words
+
+    def wire(self, model, slot=None):
+        model.wait_flag = None if slot is None else self.ready_word + 4 * slot
+        model.start_signal = None if slot is None else self.start_word
+
+    def _slot_free(self, main, side, overlap):
+        if overlap and self.starts >= 2:
+            L.check(self.lib.eagcn_stream_wait_counter(self.start_word, self.starts & 0xFFFFFFFF, side.cuda_stream),
+                    'eagcn_stream_wait_counter')
+
+    def ready(self, slot, main, side, overlap):
+        L.check(self.lib.eagcn_stream_signal_flag(self.ready_word + 4 * slot, side.cuda_stream), 'eagcn_stream_signal_flag')
+
+    def reset(self):
+        """No flag may stay set, and the start word holds the count of the forwards that the host counted."""
+        v = self.starts & 0xFFFFFFFF
+        self.words.synchronize()
+        self.words.zero_ready()
+        self.words.set_start(v - 2 ** 32 if v >= 2 ** 31 else v)       # (the count as the int32 device word holds it)
+        self.words.synchronize()
+
+
+class _DeviceWords:
+    """The hand-off words of one runner on the device: two ready flags and the start counter (FlagHandoff `words`)."""
+
+    def __init__(self, device):
+        self.device = device
+        self.ready = torch.zeros(2, dtype=torch.int32, device=device)
+        self.start = torch.zeros(1, dtype=torch.int32, device=device)
+        self.zero_ready, self.set_start = self.ready.zero_, self.start.fill_
+
+    def synchronize(self):
+        torch.cuda.synchronize(self.device)
+
+
+def _make_handoff(device):
+    if not _ready_flag_ok(device):
+        return EventHandoff(torch.cuda.Event)
+    w = _DeviceWords(device)
+    return FlagHandoff(torch.cuda.Event, L.load(), w.ready.data_ptr(), w.start.data_ptr(), w)
+
+
+def raise_sticky(lib):
+    """The two sticky host-mapped words of the library (plain host reads, no synchronisation): the replay loop makes no C call per
+    step, so every batch polls them here."""
+    if lib.eagcn_stream_wait_timeouts():
+        raise L.EagcnHipError('a step waited 2 s for its batch-ready flag (the index stream did not run beside the step: shared '
+                              'hardware queue?): results of that step are invalid; set EAGCN_READY_FLAG=0 (stream events) and '
+                              'call eagcn_stream_wait_reset()')
+    if lib.eagcn_gemm_sk_failed():        # a timed-out stream-K hand-off (csrc/gemm3.hip) poisons its tile
+        raise L.EagcnHipError('a stream-K GEMM hand-off timed out in an earlier step (a contributor wave was not '
+                              'co-resident with its owner): the gradients of that step are NaN-poisoned; '
+                              'eagcn_gemm_sk_reset_failed() clears the flag')
+
+
+class BatchRing:
+    """Per batch in flight, `n` entries: the pinned validity words of its index build (`meta`), the event behind its
+    preparation (behind which the words are valid and the staging is free again), whether it came as a bond list (the wording of
+    its report) and the pinned staging of its dropout seeds (`seeds`: the source of an asynchronous copy)."""
+
+    def __init__(self, n, row_cap, edge_cap):
+        self.row_cap, self.edge_cap = row_cap, edge_cap
+        self.meta = [torch.zeros(L.META_WORDS, dtype=torch.int32).pin_memory() for _ in range(n)]
+        self.seeds = [torch.zeros(8, dtype=torch.int64).pin_memory() for _ in range(n)]
+        self.event = [None] * n
+        self.compact = [False] * n
+
+    def filed(self, i, event, compact=False):
+        self.event[i], self.compact[i] = event, compact
+
+    def _settle(self, i, prefix):
+        """Entry `i` is finished: free it, and raise what its words say against the batch."""
+        self.event[i] = None
+        bad = L.index_error(self.meta[i].tolist(), self.row_cap, self.edge_cap, self.compact[i])
+        if bad:
+            raise L.EagcnHipError(prefix + bad)
+
+    def poll(self):
+        """The sticky words, and every entry whose batch has finished (no wait)."""
+        raise_sticky(L.load())
+        for i, ev in enumerate(self.event):
+            if ev is not None and ev.query():
+                self._settle(i, 'a previous batch: ')
+
+    def free(self, i, prefix='a previous batch: '):
+        """Entry `i` is about to be reused: wait for it alone -- the oldest batch in flight.  (Waiting for every entry waits for
+        the NEWEST batch's index build too and pulls the host back to less than one step ahead of the GPU every time the ring
+        wraps: 38 us of idle main stream per 0.4 ms step at configs[1], profiles/r06_streams_before.txt.)"""
+        if self.event[i] is not None:
+            self.event[i].synchronize()
+            self._settle(i, prefix)
+
+    def check_now(self, i):
+        """validate='sync': wait for THIS batch's index kernels and raise before anything consumes the index."""
+        self.free(i, '')
+
+    def rows(self, i):
+        """Packed rows of entry `i`'s batch (one host wait)."""
+        if self.event[i] is not None:
+            self.event[i].synchronize()
+        return int(self.meta[i][L.META_T])
+
+
+def grads_before(params, views):
+    """In front of a step that OVERWRITES `views` (one per parameter or None: where its gradient will stand): what grads_attach
+    needs to attach them as ``loss.backward()`` would.  Returns (todo, kept); `kept` is None when no parameter has a .grad -- the
+    usual case after zero_grad(set_to_none), which costs no device work -- and otherwise holds a copy of every view that IS the
+    .grad of its parameter (accumulation across steps).  Frozen tensors among `params` (the constant attention weights of
+    Vanilla_GCN.hot_params) never get a .grad: zero_grad would not clear it and every later step would accumulate."""
+    todo = [(p, v, p.grad) for p, v in zip(params, views) if v is not None and p.requires_grad]
+    if all(g is None for _, _, g in todo):
+        return todo, None
+    return todo, [v.clone() if g is v else None for _, v, g in todo]
+
+
+def grads_attach(todo, kept):
+    if kept is None:
+        for p, v, _ in todo:
+            p.grad = v
+        return
+    for (p, v, g), k in zip(todo, kept):
+        if g is None:
+            p.grad = v
+        elif g is v:
+            v.add_(k)
+        else:
+            g.add_(v)                                         # a gradient tensor of the caller's: accumulate into it
 
 
 class StaticIndex:
@@ -161,15 +349,12 @@ class GraphRunner:
         self.slots = [StaticIndex(B, N, channels, device, row_cap if row_cap else B * N, edge_cap, rel_c, structure) for _ in range(2)]
         self.rel_vectors = None        # per batch: the code books of a general batch (set by EAGCN._graph_runner)
         self.index = self.slots[0]
-        self.graphs = [[None, None, None], [None, None, None]]   # per slot: [forward, backward, whole step (fused loss)]
-        self.step_kind = [None, None]
-        self.fwd_done = None                                  # main-stream position after the last forward graph
+        # captured graphs by place: (slot, 'fwd' | 'bwd' | 'step') or (slot, 'attr', steps, baseline) -> (tag, graph); a place
+        # whose tag differs from the one asked for (another loss, optimizer, ...) is captured anew
+        self.graphs = {}
         self.dropout = float(dropout)
         self.seeds_dev = [torch.zeros(8, dtype=torch.int64, device=device) for _ in range(2)]
-        self.seeds_host = [torch.zeros(8, dtype=torch.int64).pin_memory() for _ in range(_RING)]
-        self.meta_host = [torch.zeros(L.META_WORDS, dtype=torch.int32).pin_memory() for _ in range(_RING)]
-        self.meta_event = [None] * _RING
-        self.meta_compact = [False] * _RING    # per ring slot: the batch came as a bond list (the wording of its validity report)
+        self.ring = BatchRing(_RING, self.index.T, self.index.E)
         self.step = 0
         self.cur = 0
         self.t_hint = None             # packed rows of the first batch (_set_row_hint): the size hint of every captured launch
@@ -177,22 +362,8 @@ class GraphRunner:
         self.generation = 0
         self.size_static = [torch.ones(B, dtype=torch.int64, device=device) for _ in range(2)]
         self.dp_group = None
-        self.fwd_sig = torch.zeros(1, dtype=torch.int32, device=device)     # bumped by every executed forward (eagcn_model.fwd_signal)
-        # the next batch's index build held back until this step's forward has passed its read-out (module comment at _SIDE_PLACED)
-        self.side_placed = _SIDE_PLACED == '1' or (_SIDE_PLACED == 'auto' and B * N <= _SIDE_PLACED_MAX_ROWS)
-        # per slot: "this slot's batch is prepared" -- set behind the batch's last preparatory kernel, polled and cleared by the
-        # step's first launch (eagcn_model.wait_flag)
-        self.ready = torch.zeros(2, dtype=torch.int32, device=device)
-        self.use_flag = _ready_flag_ok(device)
-        # ... and the other direction: every forward adds 1 to `start_word` in its first launch (eagcn_model.start_signal): when the
-        # n-th forward issued on the main stream has STARTED, everything issued before it -- the steps that used the slots last -- is
-        # done.  The side stream waits for that count instead of for an event recorded on the main stream between two step graphs.
-        # markers[k]: what "the main stream's work up to the step before (k = 1) / before that (k = 0) is done" means:
-        # ('count', n) or, without the flags, ('event', ev)
-        self.start_word = torch.zeros(1, dtype=torch.int32, device=device)
-        self.starts_issued = 0
-        self.markers = [None, None]
-        self.fwd_issued = 0                                                  # ... and the number of forwards issued so far
+        self.handoff = _make_handoff(device)
+        self.use_flag = isinstance(self.handoff, FlagHandoff)  # (read by tools/replay_probe.py and the tests)
         self.cms = [self._cmodel(i) for i in range(2)]
         m = self.cms[0]
         self.saved_bytes = lib.eagcn_model_saved_bytes(self.index.ref(), C.byref(m))
@@ -225,7 +396,7 @@ class GraphRunner:
         self._xout_views = [sv[xo.value:xo.value + 4 * T * ld.value].view(torch.float32).view(T, ld.value) for sv in self.saved]
         self._pad_views = [sv[po.value:po.value + 4 * ld.value].view(torch.float32) for sv in self.saved]
         self.ptrs = [t.data_ptr() for t in plan._ptr_tensors]
-        self._attr = None              # static buffers + captured graphs of atom attributions (attributions(); built on first use)
+        self._attr = None              # static buffers of atom attributions (attributions(); built on first use)
 
     def nbytes(self):
         """Device memory this runner holds (two index slots, two saved-activation blocks, scratch, gradients)."""
@@ -237,7 +408,7 @@ class GraphRunner:
     def release(self):
         """Drop the captured graphs and every static buffer (eviction from EAGCN._runners)."""
         torch.cuda.synchronize(self.device)
-        self.graphs = [[None, None, None], [None, None, None]]
+        self.graphs = {}
         self.saved, self.scratch, self.slots, self.index = [], None, [], None
         self._xout_views, self._pad_views = [], []
         self._attr = None
@@ -272,11 +443,7 @@ class GraphRunner:
             m.layer[l].seed_dev = sd + 8 * l
         m.head_seed_dev = sd + 8 * 4
         m.input_packed = 1
-        if self.use_flag:
-            m.wait_flag = self.ready.data_ptr() + 4 * slot
-            m.start_signal = self.start_word.data_ptr()
-        if self.side_placed:
-            m.fwd_signal = self.fwd_sig.data_ptr()
+        self.handoff.wire(m, slot)
         return m
 
     def stale(self):
@@ -289,13 +456,9 @@ class GraphRunner:
         return _ptr(self.size_static[self.cur]) if self.plan.molfp else C.c_void_p(0)
 
     def _call_forward(self):
-        lib = L.load()
-        if not torch.cuda.is_current_stream_capturing():
-            self.fwd_issued += 1                              # (a captured forward counts when its graph is replayed)
-            self.starts_issued += 1
-        L.check(lib.eagcn_model_forward(self.index.ref(), C.byref(self.cms[self.cur]), C.c_void_p(0), self._size_ptr(),
-                                        _ptr(self.saved[self.cur]), self.saved_bytes, _ptr(self.scratch), self.scratch_bytes, _ptr(self.out),
-                                        _ptr(self.graph_rep), _stream()), 'eagcn_model_forward')
+        L.check(L.load().eagcn_model_forward(self.index.ref(), C.byref(self.cms[self.cur]), C.c_void_p(0), self._size_ptr(),
+                                             _ptr(self.saved[self.cur]), self.saved_bytes, _ptr(self.scratch), self.scratch_bytes,
+                                             _ptr(self.out), _ptr(self.graph_rep), _stream()), 'eagcn_model_forward')
 
     def _call_backward(self, with_head=1, hi=None, lo=0):
         """The backward of layers hi .. lo (default: all of them), behind the head's when `with_head`."""
@@ -307,116 +470,84 @@ class GraphRunner:
                                                     _ptr(self.dout), _ptr(self.dgr), self.lg, C.byref(self.hg), with_head, hi, lo,
                                                     _stream()), what)
 
-    def _capture(self):
-        """Capture both sequences (nothing executes during capture).  Called after the first step ran
-        eagerly, which also serves as the warm-up HIP needs before a capture."""
-        lib = L.load()
-        lib.eagcn_prof_enable(0)
-        if self.training and os.environ.get('EAGCN_NO_WARM_BWD', '0') != '1':
-            # the backward sequence has never run when the first slot is captured: launch it once eagerly (it only
-            # overwrites the gradient buffer and scratch), so that no kernel is launched for the first time inside a
-            # capture
-            keep = self.flat_acc.clone()              # (gradients of earlier backward passes may be attached to it)
-            self._call_backward()
-            self.flat_acc.copy_(keep)
-        _drain_collectives(self.device)
-        fwd = torch.cuda.CUDAGraph()
+    def _record(self, body):
+        """`body` captured into a new graph (nothing executes during capture)."""
+        g = torch.cuda.CUDAGraph()
         # thread_local: other threads (e.g. the RCCL watchdog of torch.distributed) may touch the HIP API during capture
-        with torch.cuda.graph(fwd, capture_error_mode='thread_local'):
-            self._call_forward()
-        bwd = None
-        if self.training:
-            bwd = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(bwd, capture_error_mode='thread_local'):
-                self._call_backward()
-        self.graphs[self.cur][0], self.graphs[self.cur][1] = fwd, bwd
+        with torch.cuda.graph(g, capture_error_mode='thread_local'):
+            body()
+        return g
+
+    def _run(self, place, body, tag=None, later=None, settle=None):
+        """THE capture site.  `body` issues one sequence that holds one hand-off-carrying forward.  First use of `place` (or of
+        `place` under this `tag`): the row hint, `body` run eagerly (this call's result, and the warm-up HIP needs before a
+        capture), then captured and kept; later uses replay the graph.  Either way one forward has been executed and is counted,
+        here and nowhere else; any failure resets the hand-off.  Returns whether this was a first use.
+
+        `later` = (place, body) of a sequence that belongs to the same slot and is replayed by a call of its own (the unfused
+        backward): it has never run when the slot is captured, so it is launched once eagerly -- it only overwrites the gradient
+        buffer and scratch -- so that no kernel is launched for the first time inside a capture, and is captured behind `body`.
+        `settle(failure)`, given when the capture may fail for reasons that are not ours (a collective inside): called with the
+        exception of the capture attempt or None; it raises, accepts the graph (None) or returns the (tag, body) to capture
+        instead."""
+        try:
+            ent = self.graphs.get(place)
+            first = ent is None or ent[0] != tag
+            if not first:
+                ent[1].replay()
+            else:
+                self._set_row_hint()
+                body()
+                if later is not None:
+                    keep = self.flat_acc.clone()              # (gradients of earlier backward passes may be attached to it)
+                    later[1]()
+                    self.flat_acc.copy_(keep)
+                _drain_collectives(self.device)
+                L.load().eagcn_prof_enable(0)
+                g, failure = None, None
+                try:
+                    g = self._record(body)
+                except Exception as e:                        # noqa: BLE001 -- handed to `settle`
+                    if settle is None:
+                        raise
+                    failure = e
+                again = settle(failure) if settle is not None else None
+                if again is not None:
+                    tag, body = again
+                    g = self._record(body)
+                self.graphs[place] = (tag, g)
+                if later is not None:
+                    self.graphs[later[0]] = (None, self._record(later[1]))
+            self.handoff.started()
+        except BaseException:
+            self.handoff.reset()
+            raise
+        return first
 
     # -- per-step entry points -----------------------------------------------------------------------
-    def _check_old_batches(self, force=False, only=None):
-        # a timed-out stream-K hand-off (csrc/gemm3.hip) poisons its tile and raises a sticky host-mapped word: the replay
-        # loop makes no C call per step, so it is polled here (a plain host read, no synchronisation)
-        if L.load().eagcn_stream_wait_timeouts():
-            raise L.EagcnHipError('a step waited 2 s for its batch-ready flag (the index stream did not run beside the step: shared '
-                                  'hardware queue?): results of that step are invalid; set EAGCN_READY_FLAG=0 (stream events) and '
-                                  'call eagcn_stream_wait_reset()')
-        if L.load().eagcn_gemm_sk_failed():
-            raise L.EagcnHipError('a stream-K GEMM hand-off timed out in an earlier step (a contributor wave was not '
-                                  'co-resident with its owner): the gradients of that step are NaN-poisoned; '
-                                  'eagcn_gemm_sk_reset_failed() clears the flag')
-        # (`only`: the forced wait is for ONE ring slot -- the one about to be reused, the oldest batch in flight.  Waiting for
-        #  every slot waits for the NEWEST batch's index build too and pulls the host back to less than one step ahead of the
-        #  GPU every time the ring wraps: the next batch's side-stream work was then issued half a step late and the step graph
-        #  waited for it, 38 us of idle main stream per 0.4 ms step at configs[1] -- profiles/r06_streams_before.txt)
-        for slot in range(_RING):
-            ev = self.meta_event[slot]
-            if ev is None:
-                continue
-            forced = force and (only is None or slot == only)
-            if not (forced or ev.query()):
-                continue
-            if forced:
-                ev.synchronize()
-            meta = self.meta_host[slot].tolist()
-            self.meta_event[slot] = None
-            bad = L.index_error(meta, self.slots[0].T, self.slots[0].E, self.meta_compact[slot])
-            if bad:
-                raise L.EagcnHipError('a previous batch: ' + bad)
-
     def _prepare(self, adj, rels, afm, size, seed, overlap=False, bonds=None, labels=None, dp_scale=None):
         """Everything of a step that reads the caller's tensors (index build, packed input, seeds, sizes, labels of a fused
         step), on the side stream when `overlap`; afterwards the main stream is ordered behind it."""
-        lib = L.load()
-        self._check_old_batches()
+        lib, ring = L.load(), self.ring
+        ring.poll()
         self.cur = cur = self.step % 2
         idx = self.index = self.slots[cur]
         main = torch.cuda.current_stream(self.device)
         slot = self.step % _RING
-        if self.meta_event[slot] is not None:                 # ring wrapped: this slot must be consumed first
-            self._check_old_batches(force=True, only=slot)
-        # main-stream position now = after the backward of the previous step; the position recorded at the
-        # PREVIOUS forward entry = after the backward of the step before it, the last user of this slot
-        if self.use_flag:
-            # the slot's last user is the step before the previous one: it is done once the forward issued LAST (the previous step's)
-            # has started -- the count of forwards issued up to now
-            slot_free = ('count', self.starts_issued) if self.starts_issued >= 2 else None
-        else:
-            # main-stream position now = after the backward of the previous step; the position recorded at the PREVIOUS forward
-            # entry = after the backward of the step before it, the last user of this slot
-            ev = torch.cuda.Event()
-            ev.record(main)
-            slot_free = self.markers[1]
-            self.markers = [self.markers[1], ('event', ev)]
+        ring.free(slot)                                       # ring wrapped: this entry must be consumed first
+        side = _index_stream(self.device) if overlap else main
+        self.handoff.begin(main, side, overlap)
         if overlap:
-            side = _index_stream(self.device)
-            if slot_free is not None and slot_free[0] == 'event':
-                side.wait_event(slot_free[1])
-            elif slot_free is not None:
-                L.check(lib.eagcn_stream_wait_counter(C.c_void_p(self.start_word.data_ptr()), slot_free[1] & 0xFFFFFFFF,
-                                                      C.c_void_p(side.cuda_stream)), 'eagcn_stream_wait_counter')
-            # ... and it is held back until the FORWARD of the previous step has finished: from there on the main
-            # stream runs the caller's loss and the head's backward -- short kernels on a few CUs -- under which
-            # the HBM-streaming index scan costs nothing (at the start of a step it would compete with the
-            # layer GEMMs and aggregations)
-            if self.fwd_done is not None and _SIDE_AFTER_FWD:
-                side.wait_event(self.fwd_done)
-            elif self.side_placed and self.fwd_issued > 0:
-                # fused steps: until the forward of the step issued last has passed its read-out (it is already enqueued on the
-                # main stream, and the main stream never waits for anything issued behind this point of the side stream)
-                L.check(lib.eagcn_stream_wait_counter(C.c_void_p(self.fwd_sig.data_ptr()), self.fwd_issued & 0xFFFFFFFF,
-                                                      C.c_void_p(side.cuda_stream)), 'eagcn_stream_wait_counter')
             for t in (afm, adj, size, labels) + tuple(rels or ()) + tuple(bonds or ()):
                 if isinstance(t, torch.Tensor) and t.is_cuda:
                     t.record_stream(side)                     # read on the side stream after this call returns
-        else:
-            side = main
         istream = C.c_void_p(side.cuda_stream)
         idx.c.n_logical = int(self.n_in) if self.n_in != idx.N else 0     # row stride of the caller's tensors / logical N
         # ---- everything that reads the caller's tensors: index, packed input, seeds, sizes -----------------
-        ops.index_build(idx.c, adj, rels, bonds, self.meta_host[slot], istream, rows=True)
-        self.meta_compact[slot] = bonds is not None
+        ops.index_build(idx.c, adj, rels, bonds, ring.meta[slot], istream, rows=True)
         L.check(lib.eagcn_model_pack_input(idx.ref(), C.byref(self.cms[cur]), _ptr(afm), _ptr(self.saved[cur]),
                                            self.saved_bytes, istream), 'eagcn_model_pack_input')
-        sh = self.seeds_host[slot]                            # pinned staging, one per ring slot (async copy source)
+        sh = ring.seeds[slot]
         sn = sh.numpy()
         sn[:4], sn[4] = L.dropout_seeds(seed)                 # (the derivation of ModelPlan.cmodel: same masks as the eager engine)
         with torch.cuda.stream(side):
@@ -435,27 +566,18 @@ class GraphRunner:
             if idx.relvec is not None:                       # code books of this batch (rows beyond them are never referenced)
                 for t, v in zip(idx.relvec, self.rel_vectors):
                     t[:v.shape[0]].copy_(v, non_blocking=True)
-        ev = torch.cuda.Event()           # meta_host[slot] is valid and seeds_host[slot] is free again after this point
+        ev = torch.cuda.Event()
         ev.record(side)
-        self.meta_event[slot] = ev
+        ring.filed(slot, ev, bonds is not None)
         if self.validate == 'sync':
-            # wait for THIS batch's index kernels (they only depend on the slot's previous user, not on the main
-            # stream's backlog) and raise on invalid input / row_cap overflow before anything consumes the index
-            ev.synchronize()
-            meta = self.meta_host[slot].tolist()
-            self.meta_event[slot] = None
-            bad = L.index_error(meta, idx.T, idx.E, bonds is not None)
-            if bad:
+            # (this batch's index kernels only depend on the slot's previous user, not on the main stream's backlog)
+            try:
+                ring.check_now(slot)
+            except L.EagcnHipError:
                 if overlap:
                     main.wait_stream(side)
-                raise L.EagcnHipError(bad)
-        if self.use_flag:
-            # (behind everything above, torch's copies included; the step's first launch waits for it on the device)
-            L.check(lib.eagcn_stream_signal_flag(C.c_void_p(self.ready.data_ptr() + 4 * cur), istream), 'eagcn_stream_signal_flag')
-        elif overlap:
-            done = torch.cuda.Event()
-            done.record(side)
-            main.wait_event(done)
+                raise
+        self.handoff.ready(cur, main, side, overlap)
         self.step += 1
         self.generation += 1
         if self.training:
@@ -471,42 +593,17 @@ class GraphRunner:
         then on: a slot that captured under another batch's count would freeze other kernels than its twin (even and odd steps would
         differ in timing and rounding).  One host wait, once per runner."""
         if self.t_hint is None:
-            slot = (self.step - 1) % _RING
-            ev = self.meta_event[slot]
-            if ev is not None:
-                ev.synchronize()
-            t = int(self.meta_host[slot][L.META_T])
+            t = self.ring.rows((self.step - 1) % _RING)
             self.t_hint = max(1, min(t, self.index.T)) if t > 0 else 0
         for sl in self.slots:
             sl.c.t_hint = self.t_hint
 
-    def _reset_ready(self):
-        """A step failed between its batch-ready signal and the launch that consumes it: no flag may stay set."""
-        if self.use_flag:
-            torch.cuda.synchronize(self.device)
-            self.ready.zero_()
-            v = self.starts_issued & 0xFFFFFFFF
-            self.start_word.fill_(v - 2 ** 32 if v >= 2 ** 31 else v)  # (an int32 tensor: the count as the device word holds it)
-            torch.cuda.synchronize(self.device)
-
     def forward(self, adj, rels, afm, size, seed, overlap=False, bonds=None):
         main = self._prepare(adj, rels, afm, size, seed, overlap, bonds)
         cur = self.cur
-        try:
-            if self.graphs[cur][0] is None:
-                self._set_row_hint()
-                self._call_forward()                          # first use of a slot: eager (and the capture warm-up)
-                self._capture()
-            else:
-                self.graphs[cur][0].replay()
-                self.fwd_issued += 1
-                self.starts_issued += 1
-        except BaseException:
-            self._reset_ready()
-            raise
+        self._run((cur, 'fwd'), self._call_forward, later=((cur, 'bwd'), self._call_backward) if self.training else None)
         if overlap:
-            self.fwd_done = torch.cuda.Event()
-            self.fwd_done.record(main)
+            self.handoff.forward_done(main)
         return self.generation
 
     def attributions(self, adj, rels, afm, size, dout, steps, baseline, bonds=None):
@@ -517,13 +614,12 @@ class GraphRunner:
         (score [B, N], attr [B, N, F])."""
         if self.training:
             raise L.EagcnHipError('graph-mode attributions run on the eval runner')
-        lib = L.load()
         if self._attr is None:
             m = self.cms[0]
             B, F = self.key[0], int(afm.shape[2])
             a = ops.attribution_buffers(self.index.ref(), m, B, self.key[1], F, self.device)
             a.update(afm=torch.zeros((B, self.key[1], F), dtype=torch.float32, device=self.device), base=torch.zeros_like(afm),
-                     dout=torch.zeros((B, m.head.nclass), dtype=torch.float32, device=self.device), graphs={})
+                     dout=torch.zeros((B, m.head.nclass), dtype=torch.float32, device=self.device), models=[])
             self._attr = a
         a = self._attr
         if afm.shape != a['afm'].shape:
@@ -532,37 +628,20 @@ class GraphRunner:
         cur = self.cur
         a['afm'].copy_(afm)
         a['dout'].copy_(dout)
-        if steps and baseline is not None:
+        based = bool(steps and baseline is not None)
+        if based:
             a['base'].copy_(baseline)
         # the first forward consumes the slot's ready flag and counts a start like every forward; the others carry no hand-off
         m_first = L.Model.from_buffer_copy(self.cms[cur])
         m_rest = L.Model.from_buffer_copy(self.cms[cur])
-        m_rest.wait_flag = m_rest.start_signal = m_rest.fwd_signal = None
+        self.handoff.wire(m_rest)
         size_ptr = self._size_ptr()
-        key = (cur, int(steps), steps and baseline is not None)
 
         def run():
             ops.attribution_launches(self.index.ref(), m_first, m_rest, size_ptr, a['saved'], a['scratch'], a['out'], a['graph_rep'],
-                                     a['afm'], a['base'] if key[2] else None, a['dout'], a['acc'], a['attr'], a['score'], steps)
-        try:
-            g = a['graphs'].get(key)
-            if g is None:
-                self._set_row_hint()
-                run()                                                 # eager: the result of this call, and the capture warm-up
-                a['models'] = a.get('models', []) + [m_first, m_rest]  # (the captured launches read these structs' values at capture)
-                lib.eagcn_prof_enable(0)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                    run()
-                a['graphs'][key] = g
-            else:
-                g.replay()
-        except BaseException:
-            self._reset_ready()
-            raise
-        if self.side_placed:
-            self.fwd_issued += 1
-        self.starts_issued += 1
+                                     a['afm'], a['base'] if based else None, a['dout'], a['acc'], a['attr'], a['score'], steps)
+        if self._run((cur, 'attr', int(steps), based), run):
+            a['models'] += [m_first, m_rest]                          # (the captured launches read these structs' values at capture)
         return a['score'].clone(), a['attr'].clone()
 
     def outputs(self):
@@ -585,50 +664,19 @@ class GraphRunner:
         elif not self.dgr_is_zero:
             self.dgr.zero_()
             self.dgr_is_zero = True
-        keep, grads = self._before_grads()
-        if self.graphs[self.cur][1] is None:
+        # the captured backward OVERWRITES flat_acc (the storage p.grad are views of)
+        todo, kept = grads_before(self.plan.params, self.acc_views)
+        ent = self.graphs.get((self.cur, 'bwd'))
+        if ent is None:
             self._call_backward()
         else:
-            self.graphs[self.cur][1].replay()
-        self._attach_grads(keep, grads)
-
-    def _before_grads(self):
-        # (frozen buffers that ride in plan.params -- the constant attention weights of Vanilla_GCN.hot_params -- never get a
-        #  .grad: optimizer.zero_grad would not clear it and every later step would take the accumulate path below)
-        grads = [p.grad if p.requires_grad else None for p in self.plan.params]
-        # the captured backward OVERWRITES flat_acc (the storage p.grad are views of); if gradients of an earlier
-        # backward are still attached (accumulation across backward calls) keep them and add afterwards
-        keep = None
-        if any(g is v for g, v in zip(grads, self.acc_views)):
-            keep = self.flat_acc.clone()
-        return keep, grads
-
-    def _attach_grads(self, keep, grads):
-        params, views = self.plan.params, self.acc_views
-        if keep is None and all(g is None for g in grads):
-            for p, v in zip(params, views):
-                if p.requires_grad:
-                    p.grad = v
-            return
-        kept = self.plan.grad_views(keep) if keep is not None else None
-        for i, (p, g, v) in enumerate(zip(params, grads, views)):
-            if not p.requires_grad:
-                continue
-            if g is None:
-                p.grad = v
-            elif g is v:
-                v.add_(kept[i])
-            else:
-                g.add_(v)                                     # a gradient tensor of the caller's: accumulate into it
+            ent[1].replay()
+        grads_attach(todo, kept)
 
     # -- fused training step: forward + loss + backward as ONE graph launch -----------------------------
     def _call_forward_step(self, kind, scaled):
         """Forward, loss and the head's backward (eagcn_model_forward_step: the head's eight stages as one launch); the layers'
         backward follows through _call_backward(with_head=0)."""
-        lib = L.load()
-        if not torch.cuda.is_current_stream_capturing():
-            self.fwd_issued += 1
-            self.starts_issued += 1
         cur = self.cur
         sl = L.StepLoss()
         sl.kind = 0 if kind == 'bce' else 1
@@ -637,9 +685,10 @@ class GraphRunner:
         sl.loss = self.loss_static[cur].data_ptr()
         sl.scale = self.scale_static[cur].data_ptr() if scaled else None       # data-parallel global normalisation (parallel.dp_loss_scale)
         sl.dout = self.dout.data_ptr()
-        L.check(lib.eagcn_model_forward_step(self.index.ref(), C.byref(self.cms[cur]), C.c_void_p(0), self._size_ptr(), _ptr(self.saved[cur]),
-                                             self.saved_bytes, _ptr(self.scratch), self.scratch_bytes, _ptr(self.out), _ptr(self.graph_rep),
-                                             C.byref(sl), _ptr(self.dgr), C.byref(self.hg), _stream()), 'eagcn_model_forward_step')
+        L.check(L.load().eagcn_model_forward_step(self.index.ref(), C.byref(self.cms[cur]), C.c_void_p(0), self._size_ptr(),
+                                                  _ptr(self.saved[cur]), self.saved_bytes, _ptr(self.scratch), self.scratch_bytes,
+                                                  _ptr(self.out), _ptr(self.graph_rep), C.byref(sl), _ptr(self.dgr), C.byref(self.hg),
+                                                  _stream()), 'eagcn_model_forward_step')
 
     def _call_backward_comm(self, comm, with_head=1):
         """The backward with the gradient average inside: head + upper layers, then the all-reduce of their bucket of the flat
@@ -683,93 +732,63 @@ class GraphRunner:
         if not self.dgr_is_zero:
             self.dgr.zero_()
             self.dgr_is_zero = True
-        keep, grads = self._before_grads()
-        if optimizer is not None and (keep is not None or any(g is not None for g in grads)):
+        todo, kept = grads_before(self.plan.params, self.acc_views)
+        if optimizer is not None and kept is not None:
             raise L.EagcnHipError('train_step(optimizer=...): the update is part of the step graph and uses this step\'s gradients; '
                                   'call optimizer.zero_grad() (set_to_none) before the step')
         self._prepare(adj, rels, afm, size, seed, overlap, bonds, labels=labels, dp_scale=scale)
-        cur = self.cur
+        cur, scaled = self.cur, scale is not None
         in_graph = comm is not None and self.comm_in_graph is not False
         # `optimizer` (eagcn_amd.optim.FlatAdam): the parameter update is the last launch of the captured step (its hyper-parameters
         # and step count live in device memory)
-        key = (kind, scale is not None, in_graph, id(optimizer) if optimizer is not None else None)
+        opt_id = id(optimizer) if optimizer is not None else None
 
         def update():
             if optimizer is not None:
                 optimizer.launch(self.flat_acc)
-        try:
-            first_eager = self.graphs[cur][2] is None or self.step_kind[cur] != key
-            if first_eager:
-                self._set_row_hint()
-                self._call_forward_step(key[0], key[1])           # eager (first use of the slot / of this loss): the warm-up
-                if in_graph:
-                    self._call_backward_comm(comm, 0)
-                else:
-                    self._call_backward(0)
-                    if comm is not None:
-                        # host-issued average of the flat buffer itself (the .grad views are attached only below: after zero_grad they are
-                        # None here and GradientAllReducer.__call__ would find nothing to reduce); the update below needs the average
-                        comm.start(self.flat_acc).wait()
-                update()
-                _drain_collectives(self.device)
-                L.load().eagcn_prof_enable(0)
-                g = torch.cuda.CUDAGraph()
-                captured, failure = True, None
-                try:
-                    with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                        self._call_forward_step(key[0], key[1])
-                        if in_graph:
-                            self._call_backward_comm(comm, 0)
-                            update()
-                        else:
-                            self._call_backward(0)
-                            if comm is None:
-                                update()
-                except L.EagcnHipError:
-                    if in_graph:
-                        comm.agree(False)                         # (the other ranks are waiting in agree() below: fail with them, not hang them)
-                    raise                                         # one of OUR launches failed: never hidden behind a re-capture
-                except Exception as e:                            # noqa: BLE001 -- the capture of the collective failed on this stack
-                    if not in_graph:
-                        raise
-                    captured, failure = False, e
-                    if optimizer is not None:
-                        optimizer.reset_ticket()                  # (an aborted capture must not leave the update's last-workgroup ticket half counted)
-                if in_graph:
-                    # every rank must replay the SAME collective sequence: a rank whose capture failed while the others replay
-                    # in-graph all-reduces would hang them.  One MIN-reduction of the success flag decides for all ranks.
-                    ok = comm.agree(captured)
-                    if ok:
-                        self.comm_in_graph = True
-                    elif _REQUIRE_IN_GRAPH:
-                        raise L.EagcnHipError('the gradient all-reduce could not be captured into the step graph on every rank '
-                                              '(EAGCN_REQUIRE_IN_GRAPH_ALLREDUCE=1): %r' % (failure,))
-                if in_graph and not self.comm_in_graph:
-                    import warnings
-                    warnings.warn('eagcn_amd: the gradient all-reduce could not be captured into the step graph (%r); falling back '
-                                  'to one host-issued all-reduce behind every replay' % (failure,), RuntimeWarning)
-                    # the collective could not be captured: step graph without it, host-issued all-reduce behind every replay
-                    _drain_collectives(self.device)
-                    self.comm_in_graph, in_graph = False, False
-                    key = (kind, scale is not None, False, key[3])
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                        self._call_forward_step(key[0], key[1])
-                        self._call_backward(0)
-                    # (the eager step above left the AVERAGED gradients in the flat buffer; the host-issued average below is then
-                    #  the identity on values that are equal on every rank)
-                self.graphs[cur][2], self.step_kind[cur] = g, key
+
+        def body(in_graph=in_graph):
+            self._call_forward_step(kind, scaled)
+            if in_graph:
+                self._call_backward_comm(comm, 0)
             else:
-                self.graphs[cur][2].replay()
-                self.fwd_issued += 1
-                self.starts_issued += 1
-        except BaseException:
-            self._reset_ready()
-            raise
-        self.fwd_done = None            # (no launch boundary after the forward any more: the next index build only waits
-                                        #  for its slot and runs under this step's kernels)
-        self._attach_grads(keep, grads)
-        if comm is not None and not in_graph and not first_eager:
+                self._call_backward(0)
+                if comm is not None:
+                    if torch.cuda.is_current_stream_capturing():
+                        return                                # (host-issued average and update behind every replay, below)
+                    # eager first use: host-issued average of the flat buffer itself (the .grad views are attached only below: after
+                    # zero_grad they are None here and GradientAllReducer.__call__ would find nothing to reduce)
+                    comm.start(self.flat_acc).wait()
+            update()
+
+        def settle(failure):
+            """The capture attempt of a step with the collective inside is over: every rank must replay the SAME collective
+            sequence (a rank whose capture failed while the others replay in-graph all-reduces would hang them), so one
+            MIN-reduction of the success flag decides for all ranks."""
+            if isinstance(failure, L.EagcnHipError):
+                comm.agree(False)                             # (the other ranks are waiting in agree() below: fail with them, not hang them)
+                raise failure                                 # one of OUR launches failed: never hidden behind a re-capture
+            if failure is not None and optimizer is not None:
+                optimizer.reset_ticket()                      # (an aborted capture must not leave the update's last-workgroup ticket half counted)
+            if comm.agree(failure is None):
+                self.comm_in_graph = True
+                return None
+            if _REQUIRE_IN_GRAPH:
+                raise L.EagcnHipError('the gradient all-reduce could not be captured into the step graph on every rank '
+                                      '(EAGCN_REQUIRE_IN_GRAPH_ALLREDUCE=1): %r' % (failure,))
+            import warnings
+            warnings.warn('eagcn_amd: the gradient all-reduce could not be captured into the step graph (%r); falling back '
+                          'to one host-issued all-reduce behind every replay' % (failure,), RuntimeWarning)
+            # step graph without the collective.  (The eager step left the AVERAGED gradients in the flat buffer; the host-issued
+            # average of the first use is then the identity on values that are equal on every rank.)
+            _drain_collectives(self.device)
+            self.comm_in_graph = False
+            return (kind, scaled, False, opt_id), lambda: body(False)
+
+        first = self._run((cur, 'step'), body, (kind, scaled, in_graph, opt_id), settle=settle if in_graph else None)
+        self.handoff.step_done()
+        grads_attach(todo, kept)
+        if comm is not None and not in_graph and not first:
             comm()                                            # one in-place average of the flat buffer, issued by the host
             update()                                          # ... and the update behind it (outside the graph in this fallback)
         return self.loss_static[cur].detach() if self.static_outputs else self.loss_static[cur].clone()

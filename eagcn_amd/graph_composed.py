@@ -24,7 +24,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .graph import StaticIndex
+from .graph import BatchRing, StaticIndex, grads_attach, grads_before, raise_sticky
 from .losses import _FusedLoss
 from .ops import index_build
 
@@ -48,29 +48,16 @@ class ComposedRunner:
         self.scale_is_one = True
         self.seeds = torch.zeros(8, dtype=torch.int64, device=device)
         self.seed_views = [self.seeds[i:i + 1] for i in range(5)]          # four layers + the head's dropout
-        self.seeds_host = torch.zeros(8, dtype=torch.int64).pin_memory()
-        self.meta_host = torch.zeros(L.META_WORDS, dtype=torch.int32).pin_memory()
-        self.pending = None            # event after the last batch's index build + uploads (its meta words are valid behind it)
+        self.ring = BatchRing(1, self.index.T, self.index.E)     # one batch in flight: its event stands behind index build + uploads
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.train_graphs = {}         # loss kind -> recorded step
         self.eval_graph = None
         self.replays = 0
 
     # ---- what reads the caller's tensors (eager) ---------------------------------------------------------------------------
-    def _raise_if_bad(self, prefix=''):
-        bad = L.index_error(self.meta_host.tolist(), self.index.T, self.index.E)
-        if bad:
-            raise L.EagcnHipError(prefix + bad)
-
     def _load(self, adj, rels, afm, size, labels, training):
-        lib = L.load()
-        if lib.eagcn_gemm_sk_failed():
-            raise L.EagcnHipError('a stream-K GEMM hand-off timed out in an earlier step; eagcn_gemm_sk_reset_failed() clears the flag')
-        if self.pending is not None:            # the pinned staging buffers are free again; deferred validation of the last batch
-            self.pending.synchronize()
-            self.pending = None
-            if self.validate != 'sync':
-                self._raise_if_bad('the previous batch: ')
+        raise_sticky(L.load())
+        self.ring.free(0, 'the previous batch: ')      # the pinned staging is free again; deferred validation of the last batch
         idx = self.index
         B, N = self.key[0], self.key[1]
         if adj.shape != (B, N, N) or afm.shape != self.afm.shape or len(rels) != idx.K:
@@ -78,7 +65,7 @@ class ComposedRunner:
                                   % (tuple(adj.shape), tuple(afm.shape), len(rels), B, N))
         stream = torch.cuda.current_stream(self.device)
         idx.c.n_logical = 0
-        index_build(idx.c, adj, rels, None, self.meta_host, C.c_void_p(stream.cuda_stream), rows=True)
+        index_build(idx.c, adj, rels, None, self.ring.meta[0], C.c_void_p(stream.cuda_stream), rows=True)
         self._keep = (adj, rels)               # (read by the kernels queued above)
         self.afm.copy_(afm, non_blocking=True)
         if size is not None:
@@ -89,15 +76,13 @@ class ComposedRunner:
             base = int(torch.randint(0, 2 ** 62, (1,)).item())          # host generator: no device synchronisation
             layer_seeds, head_seed = L.dropout_seeds(base)
             self.last_seeds = layer_seeds + [head_seed]
-            self.seeds_host.numpy()[:5] = self.last_seeds
-            self.seeds.copy_(self.seeds_host, non_blocking=True)
+            self.ring.seeds[0].numpy()[:5] = self.last_seeds
+            self.seeds.copy_(self.ring.seeds[0], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(stream)
-        self.pending = ev
+        self.ring.filed(0, ev)
         if self.validate == 'sync':
-            ev.synchronize()
-            self.pending = None
-            self._raise_if_bad()
+            self.ring.check_now(0)
 
     # ---- the recorded sequence -------------------------------------------------------------------------------------------------
     def _body(self, kind):
@@ -131,20 +116,10 @@ class ComposedRunner:
         ent = self.train_graphs.get(kind)
         if ent is None:
             ent = self.train_graphs[kind] = self._record(kind)
-        keep = []
-        for p, g in zip(self.params, ent['grads']):        # ``loss.backward()`` ACCUMULATES into an existing .grad
-            keep.append(g.clone() if (g is not None and p.grad is g) else None)
+        todo, kept = grads_before(self.params, ent['grads'])      # ``loss.backward()`` ACCUMULATES into an existing .grad
         ent['graph'].replay()
         self.replays += 1
-        for p, g, k in zip(self.params, ent['grads'], keep):
-            if g is None:
-                continue
-            if p.grad is None:
-                p.grad = g
-            elif p.grad is g:
-                g.add_(k)
-            else:
-                p.grad.add_(g)
+        grads_attach(todo, kept)
         return self._outputs(ent['loss'], ent['out'], ent['atom'], ent['grep'])
 
     def _warm_up(self, kind):

@@ -83,13 +83,18 @@ def test_one_launch_head_matches_separate_launches(task, T, B, dropout):
         assert torch.equal(sa[k], sb[k]), k
 
 
-def test_pipelined_steps_equal_synchronous_steps():
+@pytest.mark.parametrize('handoff', ['flag', 'event'])
+def test_pipelined_steps_equal_synchronous_steps(handoff, monkeypatch):
     """Sixteen fused steps issued back to back WITHOUT a synchronisation -- the host runs ahead, the index build of batch k + 1 / k + 2
     runs on the side stream under step k, slots and ring entries are reused, the batch-ready flag and the start counter
     (eagcn_model.wait_flag / start_signal) order the two streams -- over four different batches taken round-robin: every step's
     loss and the last step's gradients equal those of the same steps issued one at a time with a device synchronisation after each
     (a side stream that started one step early would clear the index of the running step: it showed as a FASTER step, not as a
-    failing test, until this one)."""
+    failing test, until this one).  Both forms of the hand-off: the device flags, and stream events (what a device that refuses the
+    flag, or EAGCN_READY_FLAG=0, gets)."""
+    import eagcn_amd.graph as G
+    if handoff == 'event':
+        monkeypatch.setattr(G, '_READY_FLAG', False)             # (read when a runner is built)
     dev = torch.device('cuda', 0)
     torch.manual_seed(21)
     a = EAGCN(28, 24, dropout=0.0, structure='Concate', n_layers=2, widths1=[32] * 5, widths2=[48] * 5, n_den1=64, n_den2=32,
@@ -114,6 +119,11 @@ def test_pipelined_steps_equal_synchronous_steps():
             p.grad = None
         losses_b.append(b.fused_step(dense, labels, 'class', bw)[0].clone())
     torch.cuda.synchronize()
+    for m in (a, b):
+        (runner,) = m._runners.values()
+        if handoff == 'flag' and not runner.use_flag:
+            pytest.skip('this device refuses the batch-ready flag (the index stream does not run beside the current stream)')
+        assert runner.use_flag == (handoff == 'flag')
     for step, (la, lb) in enumerate(zip(losses_a, losses_b)):
         assert torch.equal(la, lb), (step, float(la), float(lb))
     for (n, p), q in zip(a.named_parameters(), b.parameters()):

@@ -39,30 +39,34 @@ for _ in range(n):
     step()
 torch.cuda.synchronize()
 print('(a) normal loop            %.1f us/step' % ((time.perf_counter() - t0) / n * 1e6))
-import ctypes as C  # noqa: E402
-from eagcn_amd import _lib as L  # noqa: E402
 from eagcn_amd.ops import _index_stream  # noqa: E402
-lib = L.load()
 runner = next(iter(model._runners.values()))
-g = [runner.graphs[0][2], runner.graphs[1][2]]
+g = [runner.graphs[(0, 'step')][1], runner.graphs[(1, 'step')][1]]
 side = _index_stream(dev)
 main = torch.cuda.current_stream(dev)
+hand = runner.handoff
 
 
-def ready(slot):          # what _prepare ends with: the step graph's first launch polls this flag
-    if runner.use_flag:
-        lib.eagcn_stream_signal_flag(C.c_void_p(runner.ready.data_ptr() + 4 * slot), C.c_void_p(side.cuda_stream))
+def replay(i):
+    """One replay with the runner's own hand-off around it and no batch work: the side stream waits until the slot's last user is
+    done and raises the slot's batch-ready flag, which the step graph's first launch polls and clears.  (The flag alone, raised
+    once per replay by a host that runs many replays ahead, is raised again before the replay two back has cleared it and is
+    then missing when its own replay polls: every such replay sits out the 2 s budget of the poll.)"""
+    hand.begin(main, side, True)
+    hand.ready(i & 1, main, side, True)
+    g[i & 1].replay()
+    hand.started()
 
 
 def run(tag, between):
     for i in range(10):
-        ready(i & 1); between(i); g[i & 1].replay()
+        between(i)
+        replay(i)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(n):
-        ready(i & 1)
         between(i)
-        g[i & 1].replay()
+        replay(i)
     torch.cuda.synchronize()
     print('%-44s %.1f us/step' % (tag, (time.perf_counter() - t0) / n * 1e6))
 
