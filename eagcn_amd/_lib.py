@@ -314,6 +314,9 @@ SIGNATURES = {
     'eagcn_attr_step': (C.c_int, [C.POINTER(Batch), C.POINTER(Model), _fp, _fp, C.c_size_t, _fp, C.c_size_t, _fp, _fp, C.c_float,
                                   C.c_int, _fp, _fp]),
     'eagcn_attr_finalize': (C.c_int, [C.POINTER(Batch), C.POINTER(Model), _fp, _fp, _fp, _fp, _fp, _fp]),
+    'eagcn_layer_bond_grad': (C.c_int, [C.POINTER(Batch), C.POINTER(LayerParams), C.POINTER(LayerBufs), _fp, C.c_int, C.c_float, C.c_int,
+                                        _fp, _fp]),
+    'eagcn_bond_attr_finalize': (C.c_int, [C.POINTER(Batch), _fp, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),
     'eagcn_model_forward_step': (C.c_int, [C.POINTER(Batch), C.POINTER(Model), _fp, _fp, _fp, C.c_size_t, _fp, C.c_size_t, _fp, _fp,
                                            C.POINTER(StepLoss), _fp, C.POINTER(HeadGrads), _fp]),
     'eagcn_head_saved_bytes': (C.c_size_t, [C.POINTER(HeadParams), C.c_int]),

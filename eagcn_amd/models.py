@@ -87,6 +87,40 @@ class LazyAtomRep:
         return self.cpu()[i]
 
 
+class BondAttributions:
+    """Result of ``EAGCN.bond_attributions``: one entry per directed bond (i, j) of the batch, in the order of the batch index's row
+    lists (molecule, then i, then j ascending).  Device tensors: ``mol``, ``i``, ``j`` int32 [E]; ``per_view`` [K, E] the score of
+    every relation view; ``score`` [E] = per_view summed over the views."""
+
+    def __init__(self, B, N, mol, i, j, per_view, score, dense=None):
+        self.B, self.N = int(B), int(N)
+        self.mol, self.i, self.j, self.per_view, self.score = mol, i, j, per_view, score
+        self._dense = dense                     # [K, B, N, N] when the finalize launch scattered it
+
+    def _scatter(self, values):
+        out = torch.zeros((self.B, self.N, self.N), dtype=values.dtype, device=values.device)
+        out[self.mol.long(), self.i.long(), self.j.long()] = values
+        return out
+
+    def dense(self, view=None):
+        """[B, N, N] with the score at [molecule, i, j] and exact zeros elsewhere: the summed score (``view=None``) or the score of
+        relation view ``view``; ``view='all'``: the [K, B, N, N] stack of the views."""
+        if view is None:
+            return self._scatter(self.score)
+        if view == 'all':
+            if self._dense is None:
+                self._dense = torch.stack([self._scatter(v) for v in self.per_view])
+            return self._dense
+        k = int(view)
+        return self._dense[k] if self._dense is not None else self._scatter(self.per_view[k])
+
+    def undirected(self, view=None):
+        """[B, N, N]: (dense + dense^T) / 2 at i < j -- the mean of the two directed scores of a chemical bond -- and zeros at
+        i >= j (a bond on the diagonal has no undirected counterpart)."""
+        d = self.dense(view)
+        return torch.triu(0.5 * (d + d.transpose(-1, -2)), diagonal=1)
+
+
 class EAGCN(nn.Module):
     def __init__(self, n_bfeat, n_afeat, n_sgc1_1=None, n_sgc1_2=None, n_sgc1_3=None, n_sgc1_4=None,
                  n_sgc1_5=None, n_sgc2_1=None, n_sgc2_2=None, n_sgc2_3=None, n_sgc2_4=None, n_sgc2_5=None,
@@ -461,6 +495,19 @@ class EAGCN(nn.Module):
                 atom_representations = atom_representations.cpu()
         return out, atom_representations, graph_representation
 
+    def _target_weights(self, afms, target):
+        """[B, nclass] weights of the attributed scalar sum(out * weights): ``target`` is a task index or that tensor."""
+        B = int(afms.shape[0])
+        nclass = self.den3.weight.shape[1]
+        if isinstance(target, torch.Tensor):
+            return target.to(device=afms.device, dtype=torch.float32).reshape(B, nclass).contiguous()
+        t = int(target)
+        if not 0 <= t < nclass:
+            raise ValueError('target task %d out of range (nclass %d)' % (t, nclass))
+        dout = torch.zeros((B, nclass), dtype=torch.float32, device=afms.device)
+        dout[:, t] = 1.0
+        return dout
+
     def atom_attributions(self, adjs, afms, *rels, size, target, steps=0, baseline=None, bonds=None):
         """Per-atom attributions of a prediction -> (score [B, N], attr [B, N, n_afeat]), score = attr summed over the features.
 
@@ -478,16 +525,7 @@ class EAGCN(nn.Module):
         if steps < 0:
             raise ValueError('steps must be >= 0')
         afms = ops._need_cuda_f32(afms, 'afms').detach()
-        B = int(afms.shape[0])
-        nclass = self.den3.weight.shape[1]
-        if isinstance(target, torch.Tensor):
-            dout = target.to(device=afms.device, dtype=torch.float32).reshape(B, nclass).contiguous()
-        else:
-            t = int(target)
-            if not 0 <= t < nclass:
-                raise ValueError('target task %d out of range (nclass %d)' % (t, nclass))
-            dout = torch.zeros((B, nclass), dtype=torch.float32, device=afms.device)
-            dout[:, t] = 1.0
+        dout = self._target_weights(afms, target)
         if baseline is not None:
             baseline = ops._need_cuda_f32(baseline, 'baseline').detach()
             if baseline.shape != afms.shape:
@@ -543,6 +581,79 @@ class EAGCN(nn.Module):
             acc.add_(g, alpha=w)
         attr = (x - base) * acc
         return attr.sum(-1), attr
+
+    def bond_attributions(self, adjs, afms, *rels, size, target, mode='attention', bonds=None, dense=False):
+        """Per-bond attributions of a prediction -> ``BondAttributions`` (mol, i, j, per_view [K, E], score [E]; E directed bonds).
+
+        With A1 = sigmoid(z) * adj the attention tensor of a view (layers.py:82-83; z = the bond's attention logit) and the
+        attributed scalar sum(out * target):
+
+          ``mode='attention'``  S_k[e] = sum over the layers of A1 * d target / d A1 at the bond: gradient x attention;
+          ``mode='relation'``   S_k[e] = sum over the layers of sigmoid'(z) z * d target / d A1, which equals
+                                sum_c rel_k[b, c, i, j] * d target / d rel_k[b, c, i, j]: gradient x input of the relation tensor,
+                                for one-hot and for general (``relations='general'``) relation tensors.
+
+        ``target``: a task index or a [B, nclass] weight tensor, as ``atom_attributions``.  ``bonds``: a compact batch (``adjs`` /
+        ``rels`` are then ignored).  ``dense=True`` also scatters the per-view scores into [K, B, N, N] in the finalize launch
+        (``result.dense('all')``).  Eval mode only; the parameters' ``.grad`` and every BatchNorm buffer stay untouched.
+
+        The layers run one by one (``forward_layers``, one autograd node per layer, also for ``graph=True`` models), autograd
+        delivers the target's gradient at every layer's output, and csrc/battr.hip walks the bond lists once per layer
+        (``eagcn_layer_bond_grad``) into one accumulator, then one finalize launch.  Structures Concate, Weighted_sum and GCN
+        (attention mode: all attention values are 1 there, the score is d target / d A over the bonds) with molfp_mode sum / ave.
+        A one-directional bond into an atom beyond the last atom with a bond of its own has no entry.
+        Integrated gradients over bonds are out of scope.  The reference offers nothing comparable: its nearest output is the
+        ``A_weight`` return value (the attention values themselves, without any gradient)."""
+        if self.training:
+            raise ops.L.EagcnHipError('bond_attributions needs model.eval(): in training mode the BatchNorm batch statistics couple '
+                                      'the molecules of a batch and a per-molecule attribution is not defined')
+        if self.structure == 'GAT':
+            raise ops.L.EagcnHipError('bond_attributions: the GAT baseline has no bond relation (its attention is computed from the '
+                                      'atom features, layers.py:99-143)')
+        if self.molfp_mode == 'pool':
+            raise ops.L.EagcnHipError("bond_attributions: molfp_mode='pool' is not served: the Diff_Pooling read-out consumes the "
+                                      "attention matrix itself (layers.py:319-324), beside the layers' aggregation")
+        if mode not in ops.BOND_MODES:
+            raise ValueError("mode must be 'attention' or 'relation', got %r" % (mode,))
+        if mode == 'relation' and self.structure == 'GCN':
+            raise ops.L.EagcnHipError("bond_attributions(mode='relation'): the GCN baseline has no relation input (layers.py:205-258)")
+        afms = ops._need_cuda_f32(afms, 'afms').detach()
+        dout = self._target_weights(afms, target)
+        if bonds is None and self.relations == 'general' and self.structure in ('Concate', 'Weighted_sum'):
+            from .collate import bonds_from_dense
+            bonds = bonds_from_dense(ops._need_cuda_f32(adjs, 'adjs'), rels)
+        if bonds is not None:
+            if self.structure == 'GCN':
+                bonds = bonds.first_view()
+            else:
+                self._check_channels(bonds.channels, bonds.rel_vectors)
+            index = ops.BatchIndex.from_bonds(bonds.B, bonds.N, bonds.channels, *bonds.checked(), rel_vectors=bonds.rel_vectors,
+                                              bond_lists=True)
+        else:
+            if self.structure == 'GCN':
+                rels = rels[:1]
+            else:
+                self._check_channels([int(r.shape[1]) for r in rels])
+            index = ops.BatchIndex(adjs, rels, bond_lists=True, structure=structure_code(self.structure))
+        if afms.shape != (index.B, index.N, self.n_afeat):
+            raise ops.L.EagcnHipError('afms is %s for a batch of B=%d N=%d' % (tuple(afms.shape), index.B, index.N))
+        with torch.enable_grad():
+            outs = self.forward_layers(index, afms.requires_grad_(True))      # (every layer output then carries an autograd node)
+            x, pad_row, layout = outs[-1]
+            pad = pad_row if self.structure in ('Weighted_sum', 'GCN') else None
+            g = ops.readout(index, layout, x, pad, self.molfp_mode, size)
+            out, _ = self.head_forward(g)
+            xouts = [o[0] for o in outs]
+            nodes = [(xo.grad_fn.spec, xo.grad_fn.buffers, xo.grad_fn.saved_tensors) for xo in xouts]
+            douts = torch.autograd.grad((out * dout).sum(), xouts)            # (no parameter's .grad is touched)
+        acc = torch.zeros((index.K, index.E), dtype=torch.float32, device=afms.device)
+        for l, ((spec, buffers, saved), dx) in enumerate(zip(nodes, douts)):
+            ops.layer_bond_grad(index, spec, buffers, saved, dx, mode, acc, 1.0, first=(l == 0))
+        mol, bi, bj, score, full = ops.bond_attr_finalize(index, acc, dense)
+        live = (mol >= 0).nonzero().squeeze(1)
+        if live.numel() != mol.numel():                  # (entries no row list names: a batch without bonds, DESIGN section 8's corner)
+            mol, bi, bj, score, acc = mol[live], bi[live], bj[live], score[live], acc[:, live]
+        return BondAttributions(index.B, index.N, mol, bi, bj, acc, score, full)
 
     def release_graphs(self):
         """Destroy every captured HIP graph and static buffer of this model NOW (they are rebuilt by the next forward).  Orderly

@@ -386,9 +386,11 @@ class _LayerFn(torch.autograd.Function):
             fin = spec.in_layout.width
             if tuple(v['W'].shape) != (fin, spec.widths[k]):
                 raise L.EagcnHipError('view %d weight is %s, expected %s' % (k, tuple(v['W'].shape), (fin, spec.widths[k])))
-            if v['att_w'].numel() != index.channels[k]:
+            # (a general index counts CODES in `channels`; its channel vectors carry the relation tensor's channel count)
+            rel_c = int(index.rel_vectors[k].shape[1]) if getattr(index, 'rel_vectors', None) else index.channels[k]
+            if v['att_w'].numel() != rel_c:
                 raise L.EagcnHipError('view %d attention weight has %d channels, relation tensor has %d'
-                                      % (k, v['att_w'].numel(), index.channels[k]))
+                                      % (k, v['att_w'].numel(), rel_c))
         p = spec.cparams(training, seed, views, ave_w)
         dev, T, fp = x.device, index.T, spec.fp
         f32 = dict(dtype=torch.float32, device=dev)
@@ -506,6 +508,46 @@ def attention_dense(index, att_weights):
     out = torch.empty((index.K, index.B, index.N, index.N), dtype=torch.float32, device=index.device)
     L.check(lib.eagcn_attention_dense(index.ref(), C.byref(p), _ptr(out), _stream()), 'eagcn_attention_dense')
     return out
+
+
+BOND_MODES = {'attention': 0, 'relation': 1}
+
+
+def layer_bond_grad(index, spec, buffers, saved, dxout, mode, acc, weight=1.0, first=True):
+    """acc [K, index.E] (+)= weight * f(z) * d target / d A1 of every bond of the row lists, for ONE eval-mode layer
+    (eagcn_layer_bond_grad, csrc/battr.hip).  `saved`: the saved tensors of the layer's _LayerFn node (x, P, Y, rscale, bn, ave_w,
+    *flat parameters), `buffers` its (running_mean, running_var) pairs, `dxout` [T, ld_out] the target's gradient at the layer's
+    output.  mode: 'attention' (gradient x attention) | 'relation' (gradient x input of the relation tensor)."""
+    x, P, Y, rscale, bn, ave_w, *flat = saved
+    if not getattr(index, 'bond_lists', False):
+        raise L.EagcnHipError('bond gradients need a batch index with bond lists: BatchIndex(..., bond_lists=True)')
+    if mode not in BOND_MODES:
+        raise ValueError("mode must be 'attention' or 'relation', got %r" % (mode,))
+    dxout = _need_cuda_f32(dxout, 'dxout')
+    if tuple(dxout.shape) != (index.T, spec.out_layout.ld) or tuple(acc.shape) != (spec.K, index.E):
+        raise L.EagcnHipError('layer_bond_grad: dxout %s for %s, accumulator %s for %s'
+                              % (tuple(dxout.shape), (index.T, spec.out_layout.ld), tuple(acc.shape), (spec.K, index.E)))
+    p = spec.cparams(False, 0, _layer_views(spec.K, flat, buffers), ave_w)
+    w = L.LayerBufs()
+    w.x, w.P, w.Y, w.rscale, w.bn = x.data_ptr(), P.data_ptr(), Y.data_ptr(), rscale.data_ptr(), bn.data_ptr()
+    L.check(L.load().eagcn_layer_bond_grad(index.ref(), C.byref(p), C.byref(w), _ptr(dxout), BOND_MODES[mode], float(weight),
+                                           int(bool(first)), _ptr(acc), _stream()), 'eagcn_layer_bond_grad')
+    return acc
+
+
+def bond_attr_finalize(index, acc, dense=False):
+    """(mol, i, j int32 [E], score [E], dense [K, B, N, N] or None) of an accumulator of layer_bond_grad: the bond of every entry of
+    the row lists and its score summed over the views (eagcn_bond_attr_finalize).  Entries no row list names keep mol = -1."""
+    K, E = acc.shape
+    dev = acc.device
+    mol = torch.full((E,), -1, dtype=torch.int32, device=dev)
+    bi = torch.zeros(E, dtype=torch.int32, device=dev)
+    bj = torch.zeros(E, dtype=torch.int32, device=dev)
+    score = torch.zeros(E, dtype=torch.float32, device=dev)
+    full = torch.zeros((K, index.B, index.N, index.N), dtype=torch.float32, device=dev) if dense else None
+    L.check(L.load().eagcn_bond_attr_finalize(index.ref(), _ptr(acc), K, _ptr(mol), _ptr(bi), _ptr(bj), _ptr(score), _ptr(full),
+                                              _stream()), 'eagcn_bond_attr_finalize')
+    return mol, bi, bj, score, full
 
 
 # ------------------------------------------------------------------------------------------------

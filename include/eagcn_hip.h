@@ -36,6 +36,9 @@
  *                           den1/bn_den1/relu/dropout/den2/bn_den2/relu/den3) and its autograd backward
  *   eagcn_model_backward_input / eagcn_attr_*
  *                        <- afm.requires_grad_() (models.py:96) and autograd to the atom features; integrated gradients
+ *   eagcn_layer_bond_grad / eagcn_bond_attr_finalize
+ *                        <- nothing comparable in the reference (nearest: the A_weight return value, layers.py:318): autograd
+ *                           to A1 of layers.py:82-83 per bond and view, times the attention (or the relation input)
  *
  * Conventions: all pointers are device pointers unless named host_*; tensors are fp32,
  * contiguous, row-major; `stream` is a hipStream_t passed as void*; functions return 0 on
@@ -518,6 +521,34 @@ int eagcn_attr_step(const eagcn_batch* b, const eagcn_model* m, const int64_t* s
 /* attr[B][N][n_afeat] = (afm - baseline) * acc (0 at rows that are not stored), score[B][N] = sum over the features: one launch */
 int eagcn_attr_finalize(const eagcn_batch* b, const eagcn_model* m, const float* afm, const float* baseline, const float* acc,
                         float* attr, float* score, void* stream);
+
+/* ---- bond attribution: gradient x attention per bond (csrc/battr.hip) -----------------------------------------------------------------
+ * For an EVAL-mode layer (p->training == 0) whose forward left P, Y, rscale, bn in `w`, the gradient dxout [T][ld_out] of a scalar
+ * target at the layer's output, view k and the bond e = (i, j) of the batch index's ROW LISTS (packed rows i, j of one molecule):
+ *     dY_i[c]  = sc[c] * [sc[c] * Y_i[c] + sh[c] > 0] * dH_i[c]            (sc, sh = rows 0, 1 of the bn table)
+ *     dH_i[c]  = m_i * dxout_i[c]                   Concate (ld_out == Fp)
+ *              = ave_w[k] * dxout_i[c - off_k]      Weighted_sum (and the GCN baseline, which is a one-view Weighted_sum layer)
+ *     D[k][e]  = d target / d A1^k_ij = rscale_k[i] * < dY_i , P_j - Y_i >   over view k's columns
+ * with A1 = sigmoid(z) * adj the tensor of layers.py:82-83 and z the bond's attention logit (att_w[k][code - 1], or <att_w[k],
+ * rel_vec[k][code - 1]> for general relations).  eagcn_layer_bond_grad performs, for every entry e the row lists name,
+ *     acc[k][e] = (first ? 0 : acc[k][e]) + weight * f(z) * D[k][e]          acc: [K][b->E], 16-byte aligned
+ *     mode 0   f = sigmoid(z)                    A1 * d target / d A1: gradient x attention
+ *     mode 1   f = sigmoid(z) (1 - sigmoid(z)) z  sum_c rel[c] * d target / d rel[c]: gradient x input of the relation tensor
+ * so that one call per layer into the same accumulator sums the layers.  One wave per packed row, P_j gathered from global memory
+ * (no molecule is staged in LDS: any molecule size), no atomics: every (k, e) has one owner and repeated runs are bit-identical.
+ * Needs an index with bond lists (eagcn_batch.build_lists); a list entry whose j is not a stored row reads nothing and adds 0 (the
+ * index lists no such bond: a one-directional bond into an atom beyond nat[b] has no entry at all).  Entries of the edge arrays that
+ * no row list names are not written.  Rejected before any HIP call (EAGCN_ERR_ARG): a null pointer, mode outside {0, 1}, training
+ * mode, an index without bond lists, acc / dxout / P / Y / bn that are not 16-byte aligned.  Nothing comparable exists in the
+ * reference: its nearest output is the A_weight return value (eagcn_attention_dense).
+ *
+ * eagcn_bond_attr_finalize: for every entry e of the row lists (row-list order) mol[e], bi[e], bj[e] = (molecule, i, j) and
+ * score[e] = sum_k acc[k][e]; with `dense` non-NULL also dense[k][mol][i][j] = acc[k][e] into a [K][B][N][N] tensor the caller
+ * zero-filled (N: the row stride eagcn_model_pack_input reads).  mol / bi / bj / score: [b->E]. */
+int eagcn_layer_bond_grad(const eagcn_batch* b, const eagcn_layer_params* p, const eagcn_layer_bufs* w, const float* dxout, int mode,
+                          float weight, int first, float* acc, void* stream);
+int eagcn_bond_attr_finalize(const eagcn_batch* b, const float* acc, int K, int32_t* mol, int32_t* bi, int32_t* bj, float* score,
+                             float* dense, void* stream);
 
 /* ---- a training step's forward + loss + HEAD backward as one call (reference train.py:317-331 in front of models.py:112-120 and
  * their autograd): the model forward as eagcn_model_forward, then the loss on `out` and the backward of den3 / bn_den2 / den2 /
