@@ -3,10 +3,11 @@ from .layers import (GAT, AFM_BatchNorm, Ave_multi_view, Dense, Diff_Pooling, Gr
                      GraphConv_base, GraphConv_block, GraphConv_Layer, Vanilla_GCN)
 from .models import EAGCN, BondAttributions, Concate_GCN, Weighted_GCN, weights_init  # noqa: F401
 from .training import EvalBuffers, EvalResult, evaluate  # noqa: F401
-from .analysis import (KMeansResult, PCAResult, RepBuffers, TSNEResult, confusion_matrix, dump_atom_rep, kmeans, pca,  # noqa: F401
-                       subsample, tsne)
+from .analysis import (KMeansResult, KNNResult, PCAResult, RepBuffers, TSNEResult, confusion_matrix, continuity,  # noqa: F401
+                       dump_atom_rep, kmeans, knn, neighbor_agreement, neighbor_ranks, pca, subsample, trustworthiness, tsne)
 
 __all__ = ['EAGCN', 'Concate_GCN', 'Weighted_GCN', 'GraphConv_Layer', 'GraphConv_block', 'GraphConv_base',
            'AFM_BatchNorm', 'Ave_multi_view', 'Dense', 'Vanilla_GCN', 'GAT', 'GraphAttentionLayer', 'Diff_Pooling',
            'weights_init', 'EvalBuffers', 'EvalResult', 'evaluate', 'RepBuffers', 'dump_atom_rep', 'kmeans', 'KMeansResult',
-           'confusion_matrix', 'pca', 'PCAResult', 'tsne', 'TSNEResult', 'subsample', 'BondAttributions']
+           'confusion_matrix', 'pca', 'PCAResult', 'tsne', 'TSNEResult', 'subsample', 'BondAttributions', 'knn', 'KNNResult',
+           'neighbor_ranks', 'trustworthiness', 'continuity', 'neighbor_agreement']

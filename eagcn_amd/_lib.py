@@ -351,6 +351,10 @@ SIGNATURES = {
     'eagcn_pca_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int]),
     'eagcn_pca_cov': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, _fp, _fp, _fp, C.c_size_t, _fp]),
     'eagcn_pca_project': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, _fp]),
+    'eagcn_knn_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int]),
+    'eagcn_knn': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, _fp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, C.c_size_t,
+                            _fp]),
+    'eagcn_knn_rank': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp, C.c_size_t, _fp]),
     'eagcn_prof_enable': (None, [C.c_int]),
     'eagcn_prof_reset': (None, []),
     'eagcn_prof_ntags': (C.c_int, []),

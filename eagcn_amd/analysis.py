@@ -13,7 +13,11 @@ relocates it to the point farthest from its centre.
 
 The second half of that analysis, the two-dimensional embeddings of tsnes.py and mol_to_vec_plot.py, is here as well: ``pca`` and an
 EXACT ``tsne`` (csrc/embed.hip) over the rows of the dump -- ``tsne(d.X[subsample(d.subtype, classes, cap)])`` for atoms,
-``tsne(d.graph_rep)`` for molecules -- without a copy of the rows to the host."""
+``tsne(d.graph_rep)`` for molecules -- without a copy of the rows to the host.
+
+What one does with a learned fingerprint first, and what says whether an embedding kept the neighbourhoods, are here too (csrc/knn.hip):
+``knn`` -- the k nearest rows of every query, exactly, without an n x n matrix: ``d.index[knn(d.graph_rep, 5).indices]`` --,
+``neighbor_ranks``, scikit-learn's ``trustworthiness`` / ``continuity`` of an embedding and ``neighbor_agreement`` with a labelling."""
 import ctypes as C
 from collections import namedtuple
 
@@ -452,3 +456,114 @@ def subsample(labels, classes, cap, generator=None):
     keep = torch.zeros(lab.numel(), dtype=torch.bool, device=lab.device)
     keep[order] = (pos - first) < int(cap)
     return torch.nonzero(keep & member).view(-1)
+
+
+# ---- nearest neighbours and the trustworthiness of an embedding (csrc/knn.hip) ------------------------------------------------------
+
+KNNResult = namedtuple('KNNResult', 'indices distances')
+KNN_MAX_K = 128                                                                          # EAGCN_KNN_MAX_K of include/eagcn_hip.h
+
+
+def knn_slabs(n, m, slabs=0):
+    """The header's rule for the split of the data rows among workgroups, restated: the number of slabs a call runs with."""
+    dt, qt = -(-int(n) // 64), -(-int(m) // 64)
+    s = int(slabs) if slabs > 0 else min(-(-4096 // qt), 64)
+    s = max(1, min(s, 4096, dt))
+    per = -(-dt // s)
+    return -(-dt // per)
+
+
+def knn_workspace_bytes(n, m, F, k, slabs=0):
+    """The header's formula for eagcn_knn_workspace_bytes, restated (tests compare the two)."""
+    return _a256(8 * knn_slabs(n, m, slabs) * int(m) * int(k)) + _a256(8 * int(m) * int(k))
+
+
+def _knn_ws(lib, n, m, F, k, slabs, device):
+    return torch.empty(max(lib.eagcn_knn_workspace_bytes(n, m, F, k, slabs), 256), dtype=torch.uint8, device=device)
+
+
+def knn(X, k, queries=None, metric='sqeuclidean', exclude_self=None, slabs=0):
+    """The k nearest rows of the device tensor X [n, F] for every row of `queries` [m, F] (None: the rows of X themselves, a row not
+    being its own neighbour unless exclude_self=False), exactly: csrc/knn.hip, semantics in include/eagcn_hip.h.  Neighbours ascend by
+    (distance, row index), distances are the direct fp32 sums of `sqdist`; neither an n x n matrix nor a host synchronisation is
+    involved, and the result does not depend on `slabs` (0: chosen by the library).
+      metric 'sqeuclidean' | 'euclidean' (its square root) | 'cosine' (1 - cos: half the squared distance of L2-normalised copies).
+    Returns KNNResult(indices [m, k] int32, distances [m, k] fp32) on the device."""
+    if metric not in ('sqeuclidean', 'euclidean', 'cosine'):
+        raise ValueError("knn: metric must be 'sqeuclidean', 'euclidean' or 'cosine'")
+    X, n, F, ld = _rows(X, 'knn')
+    self_join = queries is None
+    if exclude_self is None:
+        exclude_self = self_join
+    if metric == 'cosine':
+        X = X[:, :F] / X[:, :F].norm(dim=1, keepdim=True)
+        ld = F
+    if self_join:
+        Q, m, ldq = X, n, ld
+    else:
+        Q, m, Fq, ldq = _rows(queries, 'knn')
+        if Fq != F or Q.device != X.device:
+            raise L.EagcnHipError('knn: queries [%d, %d] do not match X [%d, %d] on %s' % (m, Fq, n, F, X.device))
+        if metric == 'cosine':
+            Q = Q[:, :F] / Q[:, :F].norm(dim=1, keepdim=True)
+            ldq = F
+    k = int(k)
+    lib = L.load()
+    idx = torch.empty((m, k if 0 < k <= KNN_MAX_K else 1), dtype=torch.int32, device=X.device)
+    dist = torch.empty(idx.shape, dtype=torch.float32, device=X.device)
+    ws = _knn_ws(lib, n, m, F, k, int(slabs), X.device)
+    L.check(lib.eagcn_knn(X.data_ptr(), n, F, ld, Q.data_ptr(), m, ldq, k, int(bool(exclude_self)), int(slabs), idx.data_ptr(), dist.data_ptr(),
+                          ws.data_ptr(), ws.numel(), _stream()), 'eagcn_knn')
+    if metric == 'euclidean':
+        dist = dist.sqrt()
+    elif metric == 'cosine':
+        dist = dist * 0.5
+    return KNNResult(idx, dist)
+
+
+def neighbor_ranks(X, candidates, slabs=0):
+    """int32 [n, k]: the 1-based position of row candidates[i, c] among the neighbours of row i of X [n, F] under the order of `knn`
+    (eagcn_knn_rank); -1 where the candidate is i itself or no row of X.  No host synchronisation."""
+    X, n, F, ld = _rows(X, 'neighbor_ranks')
+    cand = torch.as_tensor(candidates)
+    if not cand.is_cuda or cand.dim() != 2 or cand.shape[0] != n or cand.dtype not in (torch.int32, torch.int64):
+        raise L.EagcnHipError('neighbor_ranks: candidates must be an integer device tensor [n = %d, k]' % n)
+    k = int(cand.shape[1])
+    if cand.dtype == torch.int64:
+        cand = cand.clamp(-1, 2 ** 31 - 1)
+    cand = cand.to(torch.int32).contiguous()
+    lib = L.load()
+    rank = torch.empty((n, max(k, 1)), dtype=torch.int32, device=X.device)
+    ws = _knn_ws(lib, n, n, F, k, int(slabs), X.device)
+    L.check(lib.eagcn_knn_rank(X.data_ptr(), n, F, ld, cand.data_ptr(), k, int(slabs), rank.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+            'eagcn_knn_rank')
+    return rank
+
+
+def trustworthiness(X, Y, n_neighbors=5):
+    """sklearn.manifold.trustworthiness(X, Y, n_neighbors=k, metric='euclidean') of the embedding Y [n, .] of the device rows X [n, F]:
+    the k neighbours of every row in Y (`knn`), their ranks in X (`neighbor_ranks`),
+        T = 1 - 2 / (n k (2 n - 3 k - 1)) * sum max(0, rank - k),
+    the sum in int64 on the device.  Returns a float: the one host synchronisation.  Ties are broken by the row index."""
+    k, n = int(n_neighbors), int(X.shape[0])
+    if Y.shape[0] != n:
+        raise ValueError('trustworthiness: X has %d rows, Y %d' % (n, Y.shape[0]))
+    if k < 1 or k >= n / 2:
+        raise ValueError('n_neighbors (%d) should be less than n_samples / 2 (%g)' % (k, n / 2))
+    ranks = neighbor_ranks(X, knn(Y, k).indices)
+    penalty = (ranks.to(torch.int64) - k).clamp_min_(0).sum()
+    return 1.0 - float(penalty.item()) * (2.0 / (n * k * (2.0 * n - 3.0 * k - 1.0)))
+
+
+def continuity(X, Y, n_neighbors=5):
+    """The trustworthiness with the two spaces exchanged: how far the neighbours in X stay neighbours in the embedding Y."""
+    return trustworthiness(Y, X, n_neighbors)
+
+
+def neighbor_agreement(indices, labels):
+    """fp64 [m]: the share of every row's neighbours (`indices` [m, k], rows of a self-join) that carry the row's own label -- the
+    reference reads 'atoms of one sub-type sit together' off its plots; this is the number.  torch ops only."""
+    lab = torch.as_tensor(labels).to(indices.device).view(-1)
+    if lab.numel() != indices.shape[0]:
+        raise ValueError('neighbor_agreement: %d labels for %d rows' % (lab.numel(), indices.shape[0]))
+    return (lab[indices.long()] == lab.unsqueeze(1)).double().mean(dim=1)

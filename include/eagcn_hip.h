@@ -31,6 +31,9 @@
  *   eagcn_rep_gather / eagcn_kmeans_*
  *                        <- dump_atom_rep train.py:213-287 (the selected atoms' representations) and the Lloyd k-means the
  *                           reference's analysis runs over them on the host (kmeans_atomrep.py)
+ *   eagcn_knn / eagcn_knn_rank
+ *                        <- the nearest molecules mol_to_vec_plot.py picks by eye; the ranks behind a trustworthiness score of
+ *                           the embeddings of tsnes.py
  *   eagcn_model_forward / eagcn_model_backward
  *                        <- EAGCN.forward models.py:96-121 end to end (layers, read-out, Graph_BN,
  *                           den1/bn_den1/relu/dropout/den2/bn_den2/relu/den3) and its autograd backward
@@ -766,6 +769,36 @@ size_t eagcn_pca_workspace_bytes(int64_t n, int F);
 int eagcn_pca_cov(const float* X, int64_t n, int F, int ld, double* mean, double* cov, void* workspace, size_t workspace_bytes, void* stream);
 int eagcn_pca_project(const float* X, int64_t n, int F, int ld, const double* mean, const float* components, int k, float* out,
                       void* stream);
+
+/* ---- exact nearest neighbours of device rows and the rank of given candidates among them (csrc/knn.hip): the similarity search the
+ * reference's mol_to_vec_plot.py does by eye, and what a trustworthiness score of an embedding needs.  On the caller's stream, no host
+ * read, no floating-point atomics, and no n x n or m x n buffer: the 64 x 64 distance tiles are consumed in registers.
+ *   The distance of query row q and data row x_j:  d(q, j) = fmaf(t, t, acc) folded over c = 0 .. F - 1 from acc = 0.0f, t = q[c] - x_j[c]
+ *     in fp32 -- one accumulator per pair, in column order: the bits of eagcn_sqdist for that pair (never the Gram identity).
+ *   The order: candidates ascend by (d, j): equal distances by the smaller row index; a NaN distance ranks behind every number (ties
+ *     again by index).  A total order: results are unique, bit-identical from run to run and THE SAME FOR EVERY VALUE OF slabs.
+ *   eagcn_knn: row i of idx / dist [m][k] holds the k first candidates of query row i of Q [m][ldq] among the rows of X [n][ldx] and
+ *     their distances (a NaN distance is stored as the quiet NaN 0x7FC00000).  Q may be X.  exclude_self = 1 (only with m == n) removes
+ *     candidate j == i BY INDEX: a duplicate of row i elsewhere stays a neighbour at distance 0.
+ *   eagcn_knn_rank: for j = cand[i][c] (int32 [n][k], device data):  rank[i][c] = 1 + #{ l != i : (d(i, l), l) < (d(i, j), j) }, the
+ *     1-based position of j among the neighbours of row i of X; -1 for a candidate equal to i or outside 0 .. n - 1 (which is never
+ *     used as an address).
+ *   Envelope: 1 <= F <= 1024, 1 <= k <= EAGCN_KNN_MAX_K, k <= n - exclude_self (eagcn_knn), 1 <= n < 2^31, 1 <= m < 2^31, ld >= F, rows
+ *     4-byte aligned, slabs >= 0; anything else returns EAGCN_ERR_ARG before any HIP call.
+ *   slabs: the data rows are cut into tiles of 64, dt = ceil(n / 64), and the tiles among S workgroups per tile of 64 query rows, so that
+ *     few queries still fill the chip.  With qt = ceil(m / 64) (eagcn_knn_rank: m = n):
+ *         S0 = slabs, or for slabs == 0  min(ceil(4096 / qt), 64);   S1 = max(1, min(S0, 4096, dt));   per = ceil(dt / S1) tiles a slab;
+ *         S = ceil(dt / per)   (no slab is empty).
+ *   workspace: 256-byte aligned, at least eagcn_knn_workspace_bytes(n, m, F, k, slabs) = a(8 S m k) + a(8 m k) bytes, a(x) = x rounded
+ *     up to a multiple of 256 (0 for arguments outside the envelope); contents are scratch.  eagcn_knn keeps the slabs' sorted lists of
+ *     64-bit keys (distance bits << 32 | index) in the first part and merges them in a second launch; eagcn_knn_rank keeps int32 counts
+ *     per slab there and the candidates' keys in the second part (three launches). */
+#define EAGCN_KNN_MAX_K 128
+size_t eagcn_knn_workspace_bytes(int64_t n, int64_t m, int F, int k, int slabs);
+int eagcn_knn(const float* X, int64_t n, int F, int ldx, const float* Q, int64_t m, int ldq, int k, int exclude_self, int slabs,
+              int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream);
+int eagcn_knn_rank(const float* X, int64_t n, int F, int ld, const int32_t* cand, int k, int slabs, int32_t* rank, void* ws,
+                   size_t ws_bytes, void* stream);
 
 /* Matrix-core path of the layer products (the reference's torch.mm and its two autograd products, layers.py:40):
  *   0 = fp32 MFMA: exact fp32 products, a k-ordered fmaf chain (csrc/gemm3.hip);
