@@ -355,6 +355,10 @@ SIGNATURES = {
     'eagcn_knn': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, _fp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, C.c_size_t,
                             _fp]),
     'eagcn_knn_rank': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp, C.c_size_t, _fp]),
+    'eagcn_silhouette_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    'eagcn_silhouette': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
+    'eagcn_cluster_moments_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    'eagcn_cluster_moments': (C.c_int, [_fp, C.c_int64, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
     'eagcn_prof_enable': (None, [C.c_int]),
     'eagcn_prof_reset': (None, []),
     'eagcn_prof_ntags': (C.c_int, []),

@@ -17,7 +17,11 @@ EXACT ``tsne`` (csrc/embed.hip) over the rows of the dump -- ``tsne(d.X[subsampl
 
 What one does with a learned fingerprint first, and what says whether an embedding kept the neighbourhoods, are here too (csrc/knn.hip):
 ``knn`` -- the k nearest rows of every query, exactly, without an n x n matrix: ``d.index[knn(d.graph_rep, 5).indices]`` --,
-``neighbor_ranks``, scikit-learn's ``trustworthiness`` / ``continuity`` of an embedding and ``neighbor_agreement`` with a labelling."""
+``neighbor_ranks``, scikit-learn's ``trustworthiness`` / ``continuity`` of an embedding and ``neighbor_agreement`` with a labelling.
+
+And the scores of a clustering, which the reference reads off its confusion-matrix plot by eye (csrc/silhouette.hip): ``silhouette_samples``
+/ ``silhouette_score`` without an n x n matrix, ``cluster_moments`` with ``davies_bouldin_score`` and ``calinski_harabasz_score``, and from
+the matrix of ``confusion_matrix`` ``adjusted_rand_score``, ``normalized_mutual_info_score`` and ``purity``."""
 import ctypes as C
 from collections import namedtuple
 
@@ -567,3 +571,215 @@ def neighbor_agreement(indices, labels):
     if lab.numel() != indices.shape[0]:
         raise ValueError('neighbor_agreement: %d labels for %d rows' % (lab.numel(), indices.shape[0]))
     return (lab[indices.long()] == lab.unsqueeze(1)).double().mean(dim=1)
+
+
+# ---- scores of a clustering (csrc/silhouette.hip) -----------------------------------------------------------------------------------
+
+SilhouetteResult = namedtuple('SilhouetteResult', 'samples score cluster_means counts n_ignored')
+ClusterMoments = namedtuple('ClusterMoments', 'centers scatter wss counts')
+SIL_MAX_K = 256                                                                          # EAGCN_SIL_MAX_K of include/eagcn_hip.h
+
+
+def silhouette_slabs(n, k, slabs=0):
+    """The header's rule for the split of a silhouette call's data tiles -- at most ceil(n / 64) + k, every cluster cut into tiles of
+    its own -- among workgroups, restated: the number of slabs a call runs with."""
+    return knn_slabs(64 * (-(-int(n) // 64) + int(k)), n, slabs)
+
+
+def _sort_bytes(n, k):
+    w0 = min(-(-n // 1024), 1024)
+    chunk = -(-(-(-n // w0)) // 64) * 64
+    w = -(-n // chunk)
+    return _a256(4 * w * (k + 1)) + _a256(4 * w * k) + 2 * _a256(4 * (k + 1)) + _a256(4 * n)
+
+
+def silhouette_workspace_bytes(n, F, k, slabs=0):
+    """The header's formula for eagcn_silhouette_workspace_bytes, restated (tests compare the two)."""
+    n, k = int(n), int(k)
+    tb = -(-n // 64) + k
+    return _sort_bytes(n, k) + _a256(16 * tb) + _a256(8 * k) + _a256(8 * silhouette_slabs(n, k, slabs) * n * k)
+
+
+def cluster_moments_workspace_bytes(n, F, k):
+    """The header's formula for eagcn_cluster_moments_workspace_bytes, restated (tests compare the two)."""
+    n, F, k = int(n), int(F), int(k)
+    R = min(-(-n // 8192), 16)
+    return _sort_bytes(n, k) + _a256(8 * R * k * F) + _a256(16 * R * k)
+
+
+def _labels(labels, n, device, what):
+    lab = torch.as_tensor(labels)
+    if not lab.is_cuda or lab.is_floating_point() or lab.dtype == torch.bool or lab.dim() != 1 or lab.numel() != n or lab.device != device:
+        raise L.EagcnHipError('%s: labels must be an integer device tensor [n = %d] beside X (eagcn_amd has no CPU path)' % (what, n))
+    if lab.dtype != torch.int32:
+        lab = lab.clamp(-1, 2 ** 31 - 1).to(torch.int32)
+    return lab.contiguous()
+
+
+def silhouette_samples(X, labels, n_clusters, slabs=0):
+    """sklearn.metrics.silhouette_samples(X, labels, metric='euclidean') of the device rows X [n, F] under the labelling `labels` (any
+    integer device tensor, e.g. kmeans(...).labels) with the clusters 0 .. n_clusters - 1 (the host must know k: no device read), exactly:
+    csrc/silhouette.hip, semantics in include/eagcn_hip.h.  Distances are the square roots of `sqdist`'s fp32 sums, all sums fp64 in a
+    fixed order; neither an n x n matrix nor a host synchronisation is involved.  A row whose label is outside 0 .. n_clusters - 1 is
+    left out on both sides (its sample is NaN): silhouette_samples(X, torch.where(keep, labels, -1), k) scores a selection without a
+    copy of the rows.  Returns SilhouetteResult(samples [n] fp64, score [] fp64 (the mean over the scored rows; NaN with fewer than two
+    non-empty clusters), cluster_means [k] fp64, counts [k] int64, n_ignored [] int64) on the device."""
+    X, n, F, ld = _rows(X, 'silhouette_samples')
+    k = int(n_clusters)
+    lab = _labels(labels, n, X.device, 'silhouette_samples')
+    lib = L.load()
+    kk = k if 2 <= k <= SIL_MAX_K else 2
+    samples = torch.empty(n, dtype=torch.float64, device=X.device)
+    means = torch.empty(kk, dtype=torch.float64, device=X.device)
+    counts = torch.empty(kk, dtype=torch.int64, device=X.device)
+    stats = torch.empty(4, dtype=torch.float64, device=X.device)
+    ws = torch.empty(max(lib.eagcn_silhouette_workspace_bytes(n, F, k, int(slabs)), 256), dtype=torch.uint8, device=X.device)
+    L.check(lib.eagcn_silhouette(X.data_ptr(), n, F, ld, lab.data_ptr(), k, int(slabs), samples.data_ptr(), means.data_ptr(), counts.data_ptr(),
+                                 stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), 'eagcn_silhouette')
+    return SilhouetteResult(samples, stats[0], means, counts, stats[3].to(torch.int64))
+
+
+def _check_number_of_labels(n_labels, n_samples):
+    if not 1 < n_labels < n_samples:
+        raise ValueError('Number of labels is %d. Valid values are 2 to n_samples - 1 (inclusive)' % n_labels)
+
+
+def silhouette_score(X, labels, n_clusters):
+    """sklearn.metrics.silhouette_score(X, labels, metric='euclidean'): the mean of `silhouette_samples` over the scored rows.  Returns
+    a float: the one host synchronisation.  ValueError as scikit-learn's when fewer than two clusters are non-empty or every scored row
+    is alone in its cluster."""
+    r = silhouette_samples(X, labels, n_clusters)
+    score, n_labels, n_scored = torch.stack([r.score, (r.counts > 0).sum().double(), r.counts.sum().double()]).tolist()
+    _check_number_of_labels(int(n_labels), int(n_scored))
+    return score
+
+
+def cluster_moments(X, labels, n_clusters):
+    """Per cluster of the labelling `labels` (as for silhouette_samples) of the device rows X [n, F], in fp64 on the device
+    (eagcn_cluster_moments): ClusterMoments(centers [k, F] the centroids, scatter [k] the mean Euclidean distance of a cluster's rows to
+    its centre, wss [k] the sum of their squared distances, counts [k] int64).  centers and scatter of an empty cluster are NaN.  No
+    host synchronisation."""
+    X, n, F, ld = _rows(X, 'cluster_moments')
+    k = int(n_clusters)
+    lab = _labels(labels, n, X.device, 'cluster_moments')
+    lib = L.load()
+    kk = k if 2 <= k <= SIL_MAX_K else 2
+    centers = torch.empty((kk, F), dtype=torch.float64, device=X.device)
+    scatter, wss = (torch.empty(kk, dtype=torch.float64, device=X.device) for _ in range(2))
+    counts = torch.empty(kk, dtype=torch.int64, device=X.device)
+    ws = torch.empty(max(lib.eagcn_cluster_moments_workspace_bytes(n, F, k), 256), dtype=torch.uint8, device=X.device)
+    L.check(lib.eagcn_cluster_moments(X.data_ptr(), n, F, ld, lab.data_ptr(), k, centers.data_ptr(), scatter.data_ptr(), wss.data_ptr(),
+                                      counts.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), 'eagcn_cluster_moments')
+    return ClusterMoments(centers, scatter, wss, counts)
+
+
+def davies_bouldin_from_moments(m):
+    """(score [] fp64, non-empty clusters [], rows []) on the device from ClusterMoments: sklearn.metrics.davies_bouldin_score -- the
+    mean over the non-empty clusters of max_j (scatter_i + scatter_j) / |centre_i - centre_j|, a zero centre distance counted as
+    infinite, and 0 when all scatters or all centre distances are (numpy.allclose to) 0."""
+    there = m.counts > 0
+    s = torch.where(there, m.scatter, torch.zeros_like(m.scatter))
+    cen = torch.where(there.unsqueeze(1), m.centers, torch.zeros_like(m.centers))
+    diff = cen.unsqueeze(1) - cen.unsqueeze(0)
+    d = (diff * diff).sum(dim=2).sqrt()
+    pair = there.unsqueeze(1) & there.unsqueeze(0)
+    flat = (s.abs().max() <= 1e-8) | (torch.where(pair, d, torch.zeros_like(d)).abs().max() <= 1e-8)      # np.allclose(., 0)
+    ratio = (s.unsqueeze(1) + s.unsqueeze(0)) / torch.where(d == 0, torch.full_like(d, float('inf')), d)
+    ratio = torch.where(pair, ratio, torch.full_like(ratio, float('-inf')))
+    worst = torch.where(there, ratio.max(dim=1).values, torch.zeros_like(s))
+    score = torch.where(flat, torch.zeros_like(worst.sum()), worst.sum() / there.sum())
+    return score, there.sum(), m.counts.sum()
+
+
+def calinski_harabasz_from_moments(m):
+    """(score [] fp64, non-empty clusters [], rows []) on the device from ClusterMoments: sklearn.metrics.calinski_harabasz_score =
+    (between-cluster dispersion / (k - 1)) / (within-cluster dispersion / (n - k)) over the non-empty clusters, 1 where the within-cluster
+    dispersion is 0."""
+    there = m.counts > 0
+    cnt = m.counts.double()
+    cen = torch.where(there.unsqueeze(1), m.centers, torch.zeros_like(m.centers))
+    n, k = cnt.sum(), there.sum().double()
+    mean = (cen * cnt.unsqueeze(1)).sum(dim=0) / n
+    extra = (cnt * ((cen - mean) ** 2).sum(dim=1)).sum()
+    intra = m.wss.sum()
+    score = torch.where(intra == 0, torch.ones_like(intra), extra * (n - k) / (intra * (k - 1.0)))
+    return score, there.sum(), m.counts.sum()
+
+
+def _moment_score(fn, X, labels, n_clusters):
+    score, n_labels, n_scored = torch.stack([t.double() for t in fn(cluster_moments(X, labels, n_clusters))]).tolist()
+    _check_number_of_labels(int(n_labels), int(n_scored))
+    return score
+
+
+def davies_bouldin_score(X, labels, n_clusters):
+    """sklearn.metrics.davies_bouldin_score of the device rows X under `labels` (as for silhouette_samples; empty clusters are left
+    out): `cluster_moments`, the k x k part in torch fp64 on the device.  Returns a float: the one host synchronisation."""
+    return _moment_score(davies_bouldin_from_moments, X, labels, n_clusters)
+
+
+def calinski_harabasz_score(X, labels, n_clusters):
+    """sklearn.metrics.calinski_harabasz_score of the device rows X under `labels` (as for silhouette_samples; empty clusters are left
+    out), from `cluster_moments`.  Returns a float: the one host synchronisation."""
+    return _moment_score(calinski_harabasz_from_moments, X, labels, n_clusters)
+
+
+def _contingency(cm, what):
+    cm = torch.as_tensor(cm)
+    if cm.dim() != 2 or cm.is_floating_point() or cm.dtype == torch.bool:
+        raise ValueError('%s: needs the integer [n_true, k] matrix that confusion_matrix returns' % what)
+    return cm.to(torch.int64)
+
+
+def adjusted_rand_score(cm):
+    """sklearn.metrics.adjusted_rand_score from the [n_true, k] matrix of `confusion_matrix`: the four pair counts in int64 where the
+    matrix lives (exact: n < 2^31 rows keep n^2 inside int64), one read, the quotient in Python integers as scikit-learn does.
+    Returns a float."""
+    cm = _contingency(cm, 'adjusted_rand_score')
+    n, sq = cm.sum(), (cm * cm).sum()
+    rows, cols = cm.sum(dim=1), cm.sum(dim=0)
+    c11 = sq - n
+    c01 = (cm * cols.unsqueeze(0)).sum() - sq
+    c10 = (cm * rows.unsqueeze(1)).sum() - sq
+    c00 = n * n - c01 - c10 - sq
+    tn, fp, fn, tp = torch.stack([c00, c01, c10, c11]).tolist()
+    if fn == 0 and fp == 0:
+        return 1.0
+    return 2.0 * (tp * tn - fn * fp) / ((tp + fn) * (fn + tn) + (tp + fp) * (fp + tn))
+
+
+def normalized_mutual_info_score(cm):
+    """sklearn.metrics.normalized_mutual_info_score(average_method='arithmetic') from the [n_true, k] matrix of `confusion_matrix`, in
+    fp64 where the matrix lives; empty rows and columns (classes or clusters without a row) do not count.  Returns a float."""
+    cm = _contingency(cm, 'normalized_mutual_info_score')
+    c = cm.double()
+    n, pi, pj = c.sum(), c.sum(dim=1), c.sum(dim=0)
+    nz = cm > 0
+    one = torch.ones_like(c)
+    logc = torch.log(torch.where(nz, c, one))
+    outer = pi.unsqueeze(1) * pj.unsqueeze(0)
+    log_outer = -torch.log(torch.where(nz, outer, one)) + 2.0 * torch.log(n)
+    term = (c / n) * (logc - torch.log(n)) + (c / n) * log_outer
+    term = torch.where(nz & (term.abs() >= 2.0 ** -52), term, torch.zeros_like(term))
+    mi = term.sum().clamp_min(0.0)
+
+    def entropy(p):
+        live = p > 0
+        h = -torch.where(live, (p / n) * (torch.log(torch.where(live, p, torch.ones_like(p))) - torch.log(n)), torch.zeros_like(p)).sum()
+        return torch.where(live.sum() > 1, h, torch.zeros_like(h))
+
+    mi, h_true, h_pred, n_true, n_pred = torch.stack([mi, entropy(pi), entropy(pj), (pi > 0).sum().double(), (pj > 0).sum().double()]).tolist()
+    if n_true == n_pred and n_true <= 1:
+        return 1.0
+    if n_true == 1 or n_pred == 1 or mi == 0:
+        return 0.0
+    return mi / (0.5 * (h_true + h_pred))
+
+
+def purity(cm):
+    """The share of the rows that carry the most frequent true class of their cluster, from the [n_true, k] matrix of `confusion_matrix`:
+    sum_c max_t cm[t, c] / n.  Returns a float."""
+    cm = _contingency(cm, 'purity')
+    if cm.numel() == 0:
+        raise ValueError('purity: the matrix is empty')
+    return float((cm.max(dim=0).values.sum().double() / cm.sum().double()).item())

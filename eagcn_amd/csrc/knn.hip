@@ -4,8 +4,8 @@
 // eagcn_sqdist -- and every candidate ordered by the 64-bit key (distance bits << 32 | row index): results are unique, hence
 // bit-identical from run to run and for every split of the data rows.
 //
-//   kn_tile            the 64 x 64 distance tile of em_sqdist_kernel (csrc/embed.hip): KN_KC columns of 64 query and 64 data rows
-//                      transposed into LDS, a 4 x 4 block per thread.  It is never stored: two consumers work on the registers.
+//   kn_tile            (csrc/dist_tile.h) the 64 x 64 distance tile of em_sqdist_kernel (csrc/embed.hip): KN_KC columns of 64 query and 64
+//                      data rows transposed into LDS, a 4 x 4 block per thread.  It is never stored: two consumers work on the registers.
 //   kn_search_kernel   grid (query tiles, slabs).  A query row's k best keys so far are a sorted list in LDS.  Every thread compares
 //                      its 16 distances with its four rows' k-th keys (a reject costs that one compare), passes the few that beat it
 //                      through LDS with a bit in the row's 64-bit mask, and wave 0 -- one lane per query row -- inserts them while
@@ -15,70 +15,19 @@
 //   kn_thr_kernel /    the keys of the candidates (one thread per candidate, the same fmaf chain), then per tile and query row
 //   kn_count_kernel /  integer counts of the data rows whose key is below each of them: LDS integer adds, per-slab partial counts,
 //   kn_rank_kernel     summed per candidate at the end (integer sums do not depend on their order).
-#include "common.h"
+#include "dist_tile.h"
 
 namespace eagcn {
 
-constexpr int KN_TILE = 64;          // query rows and data rows of a tile
-constexpr int KN_KC = 32;            // feature columns staged per step
-constexpr int KN_THREADS = 256;
-constexpr int KN_PADT = KN_TILE + 4; // LDS row of a transposed tile: 16-byte aligned rows
-constexpr int KN_MAX_F = 1024;
 constexpr int KN_MAX_K = EAGCN_KNN_MAX_K;
-constexpr int KN_TARGET_WGS = 4096;  // slabs = 0: as many slabs as bring the launch to this many workgroups ...
-constexpr int KN_AUTO_SLABS = 64;    // ... and at most this many
-constexpr int KN_MAX_SLABS = 4096;
 constexpr uint64_t KN_SENTINEL = 0x7FC000007FFFFFFFull;    // (NaN, 2^31 - 1): behind every candidate, n < 2^31
 constexpr uint64_t KN_INVALID = ~0ull;                     // threshold of a candidate that is the row itself or no row at all
-constexpr size_t KN_STAGE_BYTES = 2 * sizeof(float) * KN_KC * KN_PADT;
-static_assert(KN_TILE * KN_TILE == 16 * KN_THREADS, "a thread holds a 4 x 4 block of a tile");
-static_assert(KN_STAGE_BYTES % 16 == 0, "the parts behind the staging tiles stay 16-byte aligned");
 
 // the order: distances ascending (their bits, as unsigned: they are sums of squares and never negative), a NaN behind every number,
 // equal distances by the smaller row index
 __device__ __forceinline__ uint64_t kn_key(float d, int j) {
     const uint32_t b = d != d ? 0x7FC00000u : __float_as_uint(d);
     return ((uint64_t)b << 32) | (uint32_t)j;
-}
-
-// acc[u][v] = d(query row i0 + 4 ty + u, data row j0 + 4 tx + v); rows beyond m / n read as zeros.  Ends behind a barrier.
-__device__ __forceinline__ void kn_tile(const float* __restrict__ Q, int64_t m, int ldq, const float* __restrict__ X, int64_t n, int ld, int F,
-                                        int64_t i0, int64_t j0, float (*sA)[KN_PADT], float (*sB)[KN_PADT], float (&acc)[4][4]) {
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, lc = tid & 31, lr = tid >> 5;
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) acc[u][v] = 0.0f;
-    for (int c0 = 0; c0 < F; c0 += KN_KC) {
-        const int c = c0 + lc;
-#pragma unroll
-        for (int u = 0; u < KN_TILE / 8; ++u) {
-            const int r = lr + 8 * u;
-            const int64_t ra = i0 + r, rb = j0 + r;
-            sA[lc][r] = (ra < m && c < F) ? Q[(size_t)ra * ldq + c] : 0.0f;
-            sB[lc][r] = (rb < n && c < F) ? X[(size_t)rb * ld + c] : 0.0f;
-        }
-        __syncthreads();
-        auto step = [&](int k) {
-            const float4 a4 = *reinterpret_cast<const float4*>(&sA[k][ty * 4]);
-            const float4 b4 = *reinterpret_cast<const float4*>(&sB[k][tx * 4]);
-            const float a[4] = {a4.x, a4.y, a4.z, a4.w}, b[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const float d = a[u] - b[v];
-                    acc[u][v] = fmaf(d, d, acc[u][v]);
-                }
-        };
-        if (c0 + KN_KC <= F) {
-#pragma unroll 8
-            for (int k = 0; k < KN_KC; ++k) step(k);
-        } else {                                            // (the columns beyond F would add exact zeros: the same bits, less work)
-            for (int k = 0; k < F - c0; ++k) step(k);
-        }
-        __syncthreads();
-    }
 }
 
 // ---- search ------------------------------------------------------------------------------------------------------------------------
@@ -275,18 +224,10 @@ struct KnPlan { int tiles, S, per; size_t part_bytes, bytes; };
 // the split of the data rows (eagcn_hip.h): whole tiles of 64 rows, `per` tiles a slab, no empty slab
 static inline KnPlan kn_plan(int64_t n, int64_t m, int k, int slabs) {
     KnPlan p;
-    const int64_t dt = (n + KN_TILE - 1) / KN_TILE, qt = (m + KN_TILE - 1) / KN_TILE;
-    int64_t S = slabs;
-    if (S <= 0) {
-        S = (KN_TARGET_WGS + qt - 1) / qt;
-        if (S > KN_AUTO_SLABS) S = KN_AUTO_SLABS;
-    }
-    if (S > KN_MAX_SLABS) S = KN_MAX_SLABS;
-    if (S > dt) S = dt;
-    if (S < 1) S = 1;
-    p.tiles = (int)dt;
-    p.per = (int)((dt + S - 1) / S);
-    p.S = (int)((dt + p.per - 1) / p.per);
+    const KnSlabs sl = kn_slabs((n + KN_TILE - 1) / KN_TILE, (m + KN_TILE - 1) / KN_TILE, slabs);
+    p.tiles = sl.tiles;
+    p.per = sl.per;
+    p.S = sl.S;
     p.part_bytes = align256((size_t)8 * p.S * (size_t)m * k);
     p.bytes = p.part_bytes + align256((size_t)8 * (size_t)m * k);
     return p;

@@ -34,6 +34,9 @@
  *   eagcn_knn / eagcn_knn_rank
  *                        <- the nearest molecules mol_to_vec_plot.py picks by eye; the ranks behind a trustworthiness score of
  *                           the embeddings of tsnes.py
+ *   eagcn_silhouette / eagcn_cluster_moments
+ *                        <- nothing in the reference, which reads the confusion matrix of kmeans_atomrep.py by eye: the
+ *                           scores of a clustering (sklearn.metrics silhouette, Davies-Bouldin, Calinski-Harabasz)
  *   eagcn_model_forward / eagcn_model_backward
  *                        <- EAGCN.forward models.py:96-121 end to end (layers, read-out, Graph_BN,
  *                           den1/bn_den1/relu/dropout/den2/bn_den2/relu/den3) and its autograd backward
@@ -799,6 +802,48 @@ int eagcn_knn(const float* X, int64_t n, int F, int ldx, const float* Q, int64_t
               int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream);
 int eagcn_knn_rank(const float* X, int64_t n, int F, int ld, const int32_t* cand, int k, int slabs, int32_t* rank, void* ws,
                    size_t ws_bytes, void* stream);
+
+/* ---- scores of a clustering of device rows (csrc/silhouette.hip): the silhouette coefficient of every row, and the cluster moments from
+ * which the Davies-Bouldin and Calinski-Harabasz indices follow -- the numbers behind the confusion matrix the reference's
+ * kmeans_atomrep.py reads by eye.  On the caller's stream, no host read, no floating-point atomics, no n x n buffer; the distance front end
+ * is the 64 x 64 tile of eagcn_knn (csrc/dist_tile.h), consumed in registers.
+ *   labels [n] int32, device data.  A row whose label is outside 0 .. k - 1 takes no part: it is neither scored nor a member of a cluster.
+ *   eagcn_silhouette: sklearn.metrics.silhouette_samples(metric='euclidean').
+ *     d(i, j) = the correctly rounded fp32 square root of the fp32 squared distance of eagcn_sqdist / eagcn_knn (one fmaf chain in column
+ *       order; d(i, i) is an exact 0).
+ *     S[i][c] = the sum of d(i, j) over the rows j of cluster c, in fp64.  The rows are brought into cluster order (row index ascending
+ *       inside a cluster; a permutation, X is not copied) and every cluster is cut into data tiles of 64 of its own rows, T <= tb =
+ *       ceil(n / 64) + k tiles in all.  The tiles are cut into slabs by the rule of eagcn_knn with dt = tb and qt = ceil(n / 64):
+ *           S0 = slabs, or for slabs == 0  min(ceil(4096 / qt), 64);   S1 = max(1, min(S0, 4096, tb));   per = ceil(tb / S1);   S = ceil(tb / per)
+ *       (slabs behind the last real tile do nothing).  Within a slab a thread adds its four distances of a query row and a tile in
+ *       column order to one fp64 accumulator per (row, cluster); the 16 threads of a query row are added by a fixed xor tree when the
+ *       cluster changes or the slab ends; the slabs are added in slab order.  The order is a function of labels, n and S alone:
+ *       results are bit-identical from run to run, and equal for every value of slabs up to the rounding of fp64 sums.
+ *     With cnt[c] the rows of cluster c and own = labels[i]:  a = S[i][own] / (cnt[own] - 1),  b = min over c != own, cnt[c] > 0 of
+ *       S[i][c] / cnt[c],  samples[i] = (b - a) / max(a, b);  0 where cnt[own] == 1 and where the quotient is no number (scikit-learn's
+ *       nan_to_num);  NaN for a row outside the labelling.
+ *     cluster_mean[c] = the mean sample of cluster c (NaN for an empty one): per thread in row order, then a fixed tree.  counts[c] = cnt[c].
+ *     stats[4] = the mean sample over the scored rows (the cluster sums in cluster order; NaN when fewer than two clusters are non-empty)
+ *       | rows scored | non-empty clusters | rows outside the labelling.
+ *   eagcn_cluster_moments: centers [k][F] = the fp64 centroids (sums of the fp32 rows in cluster order, cut into R = min(ceil(n / 8192), 16)
+ *     stretches per cluster that are added in order; NaN for an empty cluster);  scatter[c] = the mean over the cluster's rows of the
+ *     fp64 Euclidean distance to its centre (differences in fp64; NaN for an empty cluster);  wss[c] = the sum of the squared distances;
+ *     counts[c].  One read of X for the centroids and one for the distances.
+ *   Envelope: 1 <= F <= 1024, 1 <= n < 2^31, ld >= F, 2 <= k <= EAGCN_SIL_MAX_K, rows 4-byte aligned, slabs >= 0; anything else returns
+ *     EAGCN_ERR_ARG before any HIP call.
+ *   workspace: 256-byte aligned, contents are scratch; 0 bytes for arguments outside the envelope.  With a(x) = x rounded up to a
+ *     multiple of 256, W0 = min(ceil(n / 1024), 1024) waves of the counting sort, chunk = ceil(n / W0) rounded up to a multiple of 64,
+ *     W = ceil(n / chunk), and  sort = a(4 W (k + 1)) + a(4 W k) + 2 a(4 (k + 1)) + a(4 n)  (histograms, offsets, cluster and tile
+ *     offsets, the permutation):
+ *         eagcn_silhouette_workspace_bytes(n, F, k, slabs) = sort + a(16 tb) + a(8 k) + a(8 S n k)      (tiles, cluster sums, part [S][n][k])
+ *         eagcn_cluster_moments_workspace_bytes(n, F, k)   = sort + a(8 R k F) + a(16 R k) */
+#define EAGCN_SIL_MAX_K 256
+size_t eagcn_silhouette_workspace_bytes(int64_t n, int F, int k, int slabs);
+int eagcn_silhouette(const float* X, int64_t n, int F, int ld, const int32_t* labels, int k, int slabs, double* samples, double* cluster_mean,
+                     int64_t* counts, double* stats, void* ws, size_t ws_bytes, void* stream);
+size_t eagcn_cluster_moments_workspace_bytes(int64_t n, int F, int k);
+int eagcn_cluster_moments(const float* X, int64_t n, int F, int ld, const int32_t* labels, int k, double* centers, double* scatter,
+                          double* wss, int64_t* counts, void* ws, size_t ws_bytes, void* stream);
 
 /* Matrix-core path of the layer products (the reference's torch.mm and its two autograd products, layers.py:40):
  *   0 = fp32 MFMA: exact fp32 products, a k-ordered fmaf chain (csrc/gemm3.hip);
