@@ -331,6 +331,10 @@ SIGNATURES = {
     'eagcn_eval_metrics_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int]),
     'eagcn_eval_class_metrics': (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int, _fp, C.c_size_t, _fp, _fp]),
     'eagcn_eval_reg_metrics': (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int, _fp, C.c_size_t, _fp, _fp]),
+    'eagcn_eval_agreement_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int]),
+    'eagcn_eval_agreement_splits': (C.c_int, [C.c_int64, C.c_int]),
+    'eagcn_eval_reg_agreement': (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int, _fp, C.c_size_t, _fp, _fp]),
+    'eagcn_eval_class_threshold': (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int, C.c_float, _fp, C.c_size_t, _fp, _fp]),
     'eagcn_rep_gather': (C.c_int, [C.POINTER(Batch), _fp, C.POINTER(Layout), _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp,
                                    C.c_int64, _fp]),
     'eagcn_rep_gather_dense': (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp,

@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libeagcn_hip.so')
-HIP_SOURCES = ['index.hip', 'gemm.hip', 'gemm3.hip', 'gemm_bx3.hip', 'gemm_bx3w.hip', 'agg.hip', 'lagg.hip', 'lagg_in.hip', 'lagg_top.hip', 'lagg_dw.hip', 'gat.hip', 'pool.hip', 'layer.hip', 'readout.hip', 'head.hip', 'head2.hip', 'loss.hip', 'clip.hip', 'attr.hip', 'battr.hip', 'metrics.hip', 'reps.hip', 'embed.hip', 'knn.hip', 'silhouette.hip']
+HIP_SOURCES = ['index.hip', 'gemm.hip', 'gemm3.hip', 'gemm_bx3.hip', 'gemm_bx3w.hip', 'agg.hip', 'lagg.hip', 'lagg_in.hip', 'lagg_top.hip', 'lagg_dw.hip', 'gat.hip', 'pool.hip', 'layer.hip', 'readout.hip', 'head.hip', 'head2.hip', 'loss.hip', 'clip.hip', 'attr.hip', 'battr.hip', 'metrics.hip', 'agree.hip', 'reps.hip', 'embed.hip', 'knn.hip', 'silhouette.hip']
 CPP_SOURCES = ['api.cpp']
 HEADERS = ['common.h', 'kernels.h', 'lagg_kernel.h', 'gemm_x6.h', 'bx3.h', 'bx3_epi.h', 'dist_tile.h', os.path.join('..', '..', 'include', 'eagcn_hip.h')]
 ARCH = 'gfx950'

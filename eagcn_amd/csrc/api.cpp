@@ -1,4 +1,4 @@
-// Library-level pieces of the C ABI: version, error string.
+// Library-level pieces of the C ABI: version, error string; the entry points of agree.hip (argument checks in front of its launchers).
 #include <hip/hip_runtime_api.h>
 #include <stdarg.h>
 #include <stdint.h>
@@ -94,3 +94,59 @@ extern "C" size_t eagcn_struct_size(int which) {
     }
 }
 extern "C" const char* eagcn_last_error(void) { return eagcn::g_err; }
+
+// ---- agreement / thresholded metrics of an evaluation (agree.hip) ---------------------------------
+namespace eagcn {
+// as kernels.h declares them (this file is plain C++ and does not include the device helpers of common.h)
+size_t agree_workspace_bytes(int64_t rows, int T);
+int agree_splits(int64_t rows, int T);
+int64_t agree_tiles(int64_t rows);
+int launch_agree_reg(const float* scores, const float* targets, const uint8_t* valid, int64_t rows, int T, void* workspace, double* out,
+                     hipStream_t s);
+int launch_agree_class(const float* scores, const float* targets, const uint8_t* valid, int64_t rows, int T, float threshold,
+                       void* workspace, double* out, hipStream_t s);
+
+#define AGREE_CHECK_ARG(cond, ...)          \
+    do {                                    \
+        if (!(cond)) {                      \
+            ::eagcn::set_error(__VA_ARGS__); \
+            return EAGCN_ERR_ARG;           \
+        }                                   \
+    } while (0)
+
+static int agree_check(const char* fn, const float* scores, const float* targets, const uint8_t* valid, int64_t rows, int T,
+                       const void* workspace, size_t workspace_bytes, const double* out) {
+    AGREE_CHECK_ARG(scores, "%s: scores is null", fn);
+    AGREE_CHECK_ARG(targets, "%s: targets is null", fn);
+    AGREE_CHECK_ARG(valid, "%s: valid is null", fn);
+    AGREE_CHECK_ARG(workspace, "%s: workspace is null", fn);
+    AGREE_CHECK_ARG(out, "%s: out is null", fn);
+    AGREE_CHECK_ARG(rows >= 1, "%s: rows = %lld, an evaluation needs at least one", fn, (long long)rows);
+    AGREE_CHECK_ARG(T >= 1 && T <= 65535, "%s: T = %d is not in 1 .. 65535", fn, T);
+    AGREE_CHECK_ARG(rows < (int64_t(1) << 31), "%s: rows = %lld does not fit the 32-bit counters (rows < 2^31)", fn, (long long)rows);
+    AGREE_CHECK_ARG(agree_tiles(rows) * T < (int64_t(1) << 31), "%s: rows x T = %lld x %d is more than one launch takes", fn,
+                    (long long)rows, T);
+    AGREE_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "%s: workspace must be 8-byte aligned", fn);
+    AGREE_CHECK_ARG(workspace_bytes >= agree_workspace_bytes(rows, T), "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes,
+                    agree_workspace_bytes(rows, T));
+    return EAGCN_OK;
+}
+}  // namespace eagcn
+
+extern "C" size_t eagcn_eval_agreement_workspace_bytes(int64_t rows, int T) {
+    return rows < 1 || T < 1 ? 0 : eagcn::agree_workspace_bytes(rows, T);
+}
+extern "C" int eagcn_eval_agreement_splits(int64_t rows, int T) { return rows < 1 || T < 1 ? 0 : eagcn::agree_splits(rows, T); }
+
+extern "C" int eagcn_eval_reg_agreement(const float* scores, const float* targets, const uint8_t* valid, int64_t rows, int T,
+                                        void* workspace, size_t workspace_bytes, double* out, void* stream) {
+    if (int rc = eagcn::agree_check("eagcn_eval_reg_agreement", scores, targets, valid, rows, T, workspace, workspace_bytes, out)) return rc;
+    return eagcn::launch_agree_reg(scores, targets, valid, rows, T, workspace, out, (hipStream_t)stream);
+}
+
+extern "C" int eagcn_eval_class_threshold(const float* scores, const float* targets, const uint8_t* valid, int64_t rows, int T,
+                                          float threshold, void* workspace, size_t workspace_bytes, double* out, void* stream) {
+    if (int rc = eagcn::agree_check("eagcn_eval_class_threshold", scores, targets, valid, rows, T, workspace, workspace_bytes, out)) return rc;
+    AGREE_CHECK_ARG(threshold == threshold, "eagcn_eval_class_threshold: threshold is NaN");
+    return eagcn::launch_agree_class(scores, targets, valid, rows, T, threshold, workspace, out, (hipStream_t)stream);
+}

@@ -423,5 +423,15 @@ int readout_backward_pad_views(const eagcn_batch* b, const float* dg, const eagc
                                int F, int K, const uint16_t* cnt, float dropout, float* dpad, void* stream);
 int readout_backward_pad(const eagcn_batch* b, const float* dg, const eagcn_layout* lay, const int64_t* size,
                          int mode, int F, float* dpad_row, void* stream);
+// agree.hip: the two launches of eagcn_eval_reg_agreement (agree_pair_kernel, agree_reg_finalize_kernel) and of
+// eagcn_eval_class_threshold (agree_class_kernel, agree_class_finalize_kernel) on checked arguments (api.cpp checks them), the
+// workspace either takes, how many workgroups share a tile's rows in the pair kernel, and the tiles of AGR_R entries of a task
+size_t agree_workspace_bytes(int64_t rows, int T);
+int agree_splits(int64_t rows, int T);
+int64_t agree_tiles(int64_t rows);
+int launch_agree_reg(const float* scores, const float* targets, const uint8_t* valid, int64_t rows, int T, void* workspace, double* out,
+                     hipStream_t s);
+int launch_agree_class(const float* scores, const float* targets, const uint8_t* valid, int64_t rows, int T, float threshold,
+                       void* workspace, double* out, hipStream_t s);
 
 }  // namespace eagcn

@@ -30,6 +30,7 @@ class EvalBuffers:
         self.targets = torch.empty((self.cap, self.T), dtype=torch.float32, device=self.device)
         self.valid = torch.empty((self.cap, self.T), dtype=torch.uint8, device=self.device)
         self._workspace = None                             # of metrics(): sized for `cap` rows, so it is regrown with the buffers
+        self._agree_workspace = None                       # of agreement() / threshold_metrics(), likewise
 
     def append(self, logits, labels):
         B = logits.shape[0]
@@ -64,6 +65,34 @@ class EvalBuffers:
                                    self._workspace.data_ptr(), self._workspace.numel(), out.data_ptr(),
                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), name)
         return EvalResult(out, self.T, 'class' if self.classification else 'reg')
+
+    def _agree_call(self, name, n_out, *extra):
+        if self.rows < 1:
+            raise L.EagcnHipError('EvalBuffers: nothing has been appended')
+        lib = L.load()
+        if self._agree_workspace is None:
+            nbytes = lib.eagcn_eval_agreement_workspace_bytes(self.cap, self.T)
+            self._agree_workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        out = torch.empty(n_out, dtype=torch.float64, device=self.device)
+        L.check(getattr(lib, name)(self.scores.data_ptr(), self.targets.data_ptr(), self.valid.data_ptr(), self.rows, self.T, *extra,
+                                   self._agree_workspace.data_ptr(), self._agree_workspace.numel(), out.data_ptr(),
+                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), name)
+        return out
+
+    def agreement(self):
+        """How well a regression's predictions agree with the targets, per task, computed on the device (csrc/agree.hip: two
+        launches on the current stream, no host sync): R^2, Pearson r (its square is the reference's rsquared, utils.py:714), Spearman
+        rho and Kendall tau-b as an AgreementResult."""
+        if self.classification:
+            raise L.EagcnHipError('EvalBuffers.agreement: these are the buffers of a classification (threshold_metrics() is for them)')
+        return AgreementResult(self._agree_call('eagcn_eval_reg_agreement', 6 * self.T + 4), self.T)
+
+    def threshold_metrics(self, threshold=0.5):
+        """What a classification's scores are worth at a decision threshold (positive: score > threshold), per task, computed on the
+        device: log-loss, Brier score, the confusion counts and accuracy / precision / recall / F1 / MCC as a ThresholdResult."""
+        if not self.classification:
+            raise L.EagcnHipError('EvalBuffers.threshold_metrics: these are the buffers of a regression (agreement() is for them)')
+        return ThresholdResult(self._agree_call('eagcn_eval_class_threshold', 12 * self.T + 4, float(threshold)), self.T, float(threshold))
 
 
 class EvalResult:
@@ -107,6 +136,78 @@ class EvalResult:
     def as_reference(self):
         """What evaluate() returns without device_metrics: (per-task AUCs, mean AUC) or the RMSE over all outputs."""
         return (self.auc, self.mean_auc) if self.kind == 'class' else self.rmse
+
+
+class _DeviceVector:
+    """An fp64 result vector that stays on the device; the accessors read a host copy made once, by the first of them."""
+
+    def __init__(self, values, n_tasks):
+        self.values, self.T = values, int(n_tasks)
+        self._host = None
+
+    def _get(self, what):
+        if self._host is None:
+            self._host = self.values.cpu().tolist()
+        return self._host
+
+    def _block(self, what, k):
+        return self._get(what)[k * self.T:(k + 1) * self.T]
+
+
+class AgreementResult(_DeviceVector):
+    """What EvalBuffers.agreement() computed: `values` is the fp64 vector of include/eagcn_hip.h (r2[T] | pearson[T] | spearman[T] |
+    kendall[T] | count[T] | bad[T] | mean_r2 | mean_pearson | mean_spearman | mean_kendall).  A task with fewer than two valid entries or
+    a non-finite score or target (n_bad) is nan in all four; a constant column is nan where scipy is, and a constant targets column has
+    r2 = nan (sklearn: 0.0 or 1.0).  The means run over the tasks that are not nan."""
+
+    r2 = property(lambda self: self._block('r2', 0))
+    pearson = property(lambda self: self._block('pearson', 1))
+    rsquared = property(lambda self: [v * v for v in self._block('rsquared', 1)])       # utils.py:714: linregress' r_value ** 2
+    spearman = property(lambda self: self._block('spearman', 2))
+    kendall = property(lambda self: self._block('kendall', 3))
+    count = property(lambda self: [int(v) for v in self._block('count', 4)])
+    n_bad = property(lambda self: [int(v) for v in self._block('n_bad', 5)])
+    mean_r2 = property(lambda self: self._get('mean_r2')[6 * self.T])
+    mean_pearson = property(lambda self: self._get('mean_pearson')[6 * self.T + 1])
+    mean_spearman = property(lambda self: self._get('mean_spearman')[6 * self.T + 2])
+    mean_kendall = property(lambda self: self._get('mean_kendall')[6 * self.T + 3])
+
+
+class ThresholdResult(_DeviceVector):
+    """What EvalBuffers.threshold_metrics() computed: `values` is the fp64 vector of include/eagcn_hip.h (log_loss[T] | brier[T] | tp[T] |
+    fp[T] | tn[T] | fn[T] | accuracy[T] | precision[T] | recall[T] | f1[T] | mcc[T] | bad[T] | mean_log_loss | mean_brier | mean_f1 |
+    mean_mcc), `threshold` what it was computed at.  A task without labelled entries is nan throughout and stays out of the means; a
+    labelled entry with a non-finite score makes every accessor raise, as EvalResult's do -- `values` holds nan for that task."""
+
+    def __init__(self, values, n_tasks, threshold):
+        super().__init__(values, n_tasks)
+        self.threshold = threshold
+
+    def _get(self, what):
+        host = super()._get(what)
+        for j, bad in enumerate(host[11 * self.T:12 * self.T]):
+            if bad > 0:
+                raise L.EagcnHipError('ThresholdResult.%s: task %d has %d labelled entries whose score is not finite' % (what, j, int(bad)))
+        return host
+
+    def _counts(self, what, k):
+        return [None if math.isnan(v) else int(v) for v in self._block(what, k)]
+
+    log_loss = property(lambda self: self._block('log_loss', 0))
+    brier = property(lambda self: self._block('brier', 1))
+    tp = property(lambda self: self._counts('tp', 2))
+    fp = property(lambda self: self._counts('fp', 3))
+    tn = property(lambda self: self._counts('tn', 4))
+    fn = property(lambda self: self._counts('fn', 5))
+    accuracy = property(lambda self: self._block('accuracy', 6))
+    precision = property(lambda self: self._block('precision', 7))
+    recall = property(lambda self: self._block('recall', 8))
+    f1 = property(lambda self: self._block('f1', 9))
+    mcc = property(lambda self: self._block('mcc', 10))
+    mean_log_loss = property(lambda self: self._get('mean_log_loss')[12 * self.T])
+    mean_brier = property(lambda self: self._get('mean_brier')[12 * self.T + 1])
+    mean_f1 = property(lambda self: self._get('mean_f1')[12 * self.T + 2])
+    mean_mcc = property(lambda self: self._get('mean_mcc')[12 * self.T + 3])
 
 
 def auc_per_task(scores, targets, valid):
@@ -213,11 +314,15 @@ def train_step(model, optimizer, batch, labels, task, bce_weight=None, dp_global
 
 
 @torch.no_grad()
-def evaluate(model, batches, task, n_tasks, device_metrics=False):
+def evaluate(model, batches, task, n_tasks, device_metrics=False, extended=False, threshold=0.5):
     """train.py:130-211: eval-mode forward over `batches` (iterable of (batch tuple, labels); a batch tuple that starts with a
     CompactBonds is (bonds, afms, size)); classification returns (per-task AUCs, mean AUC), regression the RMSE.  The model
     is put back into training mode afterwards, as the reference does (train.py:171, 210).  device_metrics=True: the metrics
-    (average precision and MAE among them) are computed by the HIP kernels and returned as an EvalResult, without a host sync."""
+    (average precision and MAE among them) are computed by the HIP kernels and returned as an EvalResult, without a host sync.
+    extended=True (with device_metrics=True): (EvalResult, AgreementResult) for a regression, (EvalResult, ThresholdResult at `threshold`)
+    for a classification, all computed on the device."""
+    if extended and not device_metrics:
+        raise ValueError('evaluate(extended=True) needs device_metrics=True: the extended metrics exist on the device only')
     was_training = model.training
     model.eval()
     buf = None
@@ -228,6 +333,8 @@ def evaluate(model, batches, task, n_tasks, device_metrics=False):
             buf = EvalBuffers(n_tasks, task != 'reg', out.device)
         buf.append(out, labels)
     model.train(was_training)
+    if device_metrics and extended:
+        return buf.metrics(), (buf.agreement() if task == 'reg' else buf.threshold_metrics(threshold))
     if device_metrics:
         return buf.metrics()
     scores, targets, valid = buf.views()

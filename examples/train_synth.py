@@ -50,6 +50,10 @@ def main():
                     help='--optimizer flat: a step whose gradient holds a NaN / Inf changes no parameter and no moment')
     ap.add_argument('--loader', default='dense', choices=('dense', 'compact'),
                     help="dense: the reference's collate tensors; compact: bond list + unpadded rows (collate_compact)")
+    ap.add_argument('--report-extended', action='store_true',
+                    help='after each evaluation also print, computed on the device (csrc/agree.hip): R^2, Pearson, Spearman and Kendall '
+                         'for a regression; log-loss, Brier, F1 and MCC at --threshold for a classification')
+    ap.add_argument('--threshold', type=float, default=0.5, help='decision threshold of --report-extended (positive: score > threshold)')
     args = ap.parse_args()
     w1, w2, d1, d2, lr, wd, task, T, n_bfeat, (n_med, n_max) = DATASETS[args.dataset]
     dev = torch.device('cuda', 0)
@@ -109,12 +113,22 @@ def main():
             loss = training.train_step(model, opt, b, labels, task, bce_w)
         if step % args.print_freq == 0 or step == args.steps - 1:
             # the metrics are computed on the device (csrc/metrics.hip); reading one of them is the evaluation's only host sync
-            metric = training.evaluate(model, val_set, task, T, device_metrics=True)
+            metric = training.evaluate(model, val_set, task, T, device_metrics=True, extended=args.report_extended,
+                                       threshold=args.threshold)
+            more = None
+            if args.report_extended:
+                metric, more = metric
             shown = 'val mean ROC-AUC %.4f  mean AP %.4f' % (metric.mean_auc, metric.mean_ap) if task == 'class' else \
                 'val RMSE %.4f  MAE %.4f' % (metric.rmse, metric.mae)
             dt = time.perf_counter() - t0
             print('step %4d  loss %.5f  %s  (%.1f molecules/s incl. evaluation; %d captured runner(s))'
                   % (step, float(loss), shown, (step + 1) * args.batch / dt, len(model._runners)))
+            if more is not None and task == 'class':
+                print('           at threshold %.2f: mean log-loss %.4f  Brier %.4f  F1 %.4f  MCC %.4f'
+                      % (more.threshold, more.mean_log_loss, more.mean_brier, more.mean_f1, more.mean_mcc))
+            elif more is not None:
+                print('           mean R^2 %.4f  Pearson %.4f  Spearman %.4f  Kendall %.4f'
+                      % (more.mean_r2, more.mean_pearson, more.mean_spearman, more.mean_kendall))
     if getattr(opt, 'clipping', False):
         # one device-to-host copy; a skipped step protects parameters and moments, not the BatchNorm running statistics
         print('clip_stats: %r' % (opt.clip_stats(),))

@@ -28,6 +28,9 @@
  *   eagcn_eval_append / eagcn_eval_class_metrics / eagcn_eval_reg_metrics
  *                        <- the evaluation functions train.py:130-211 (sklearn roc_curve + auc per task, RMSE; plus
  *                           average precision and MAE)
+ *   eagcn_eval_reg_agreement / eagcn_eval_class_threshold
+ *                        <- rsquared utils.py:714 (the squared Pearson coefficient), with R^2, Spearman and Kendall; the
+ *                           thresholded metrics and log-loss of a classification trained with the weighted BCE of utils.py:642-700
  *   eagcn_rep_gather / eagcn_kmeans_*
  *                        <- dump_atom_rep train.py:213-287 (the selected atoms' representations) and the Lloyd k-means the
  *                           reference's analysis runs over them on the host (kmeans_atomrep.py)
@@ -664,6 +667,44 @@ int eagcn_eval_class_metrics(const float* scores, const float* targets, const ui
                              size_t workspace_bytes, double* out, void* stream);
 int eagcn_eval_reg_metrics(const float* scores, const float* targets, const uint8_t* valid, int64_t rows, int T, void* workspace,
                            size_t workspace_bytes, double* out, void* stream);
+
+/* ---- agreement of a regression with its targets, thresholded metrics of a classification, over the same buffers (csrc/agree.hip):
+ * two launches per call, no sort, no host read, no atomics, bit-identical from run to run.  A task's entries are its rows with
+ * valid != 0, n their number; comparisons are on the fp32 values (-0 == +0).
+ *   eagcn_eval_reg_agreement: out[6T + 4] doubles = r2[T] | pearson[T] | spearman[T] | kendall[T] | count[T] | bad[T] | mean_r2 |
+ *   mean_pearson | mean_spearman | mean_kendall.  With s the scores, y the targets and, per entry i, the exact 32-bit pair counts
+ *       lt_s = #{j: s_j < s_i}, eq_s = #{j: s_j == s_i} (i included), lt_y, eq_y likewise, S_i = sum_j sgn(s_i - s_j) sgn(y_i - y_j):
+ *     r2 = 1 - sum (y - s)^2 / sum (y - mean y)^2                                   (sklearn r2_score(targets, scores))
+ *     pearson = sum (s - mean s)(y - mean y) / sqrt(sum (s - mean s)^2 sum (y - mean y)^2)  (scipy pearsonr; its square is the
+ *       reference's rsquared, utils.py:714) -- fp64 sums centred per tile of 256 entries, merged in tile order by the pairwise update
+ *       of Chan, Golub and LeVeque; no raw sum of squares
+ *     spearman = sum ab / sqrt(sum a^2 sum b^2), a_i = 2 lt_s + eq_s - n = 2 (average rank) - (n + 1), b_i likewise: 64-bit integer
+ *       products, summed in 64-bit integers for n <= 3 000 000 (where they provably fit), in fp64 in a fixed order beyond
+ *     kendall = tau-b = (sum_i S_i / 2) / sqrt((n0 - n1)(n0 - n2)), n0 = n (n - 1) / 2, n1 = sum (eq_s - 1) / 2, n2 = sum (eq_y - 1) / 2,
+ *       exact 64-bit integers
+ *     count = n, bad = entries whose score or target is not finite.  A task with bad > 0 or n < 2 has NaN in all four.  A constant
+ *     scores or targets column (every pair tied) gives NaN for pearson, spearman and kendall, as scipy does; a constant targets
+ *     column gives NaN for r2 -- a deviation: sklearn returns 0.0 or 1.0 there.  Each mean runs over the tasks where its metric is not
+ *     NaN (NaN if there is none).
+ *   eagcn_eval_class_threshold: an entry is labelled where valid and target is 0 or 1, predicted positive where score > threshold.
+ *   out[12T + 4] doubles = log_loss[T] | brier[T] | tp[T] | fp[T] | tn[T] | fn[T] | accuracy[T] | precision[T] | recall[T] | f1[T] |
+ *   mcc[T] | bad[T] | mean_log_loss | mean_brier | mean_f1 | mean_mcc.
+ *     log_loss = -mean(y log p + (1 - y) log(1 - p)) in fp64, p = double(score) clipped to [2^-52, 1 - 2^-52]; brier = mean((p - y)^2);
+ *     the counts are exact; a zero denominator gives 0.0 for precision, recall, f1 and mcc (sklearn's value under its default
+ *     warning).  bad = labelled entries whose score is not finite.  A task without labelled entries or with bad > 0 is NaN throughout
+ *     (bad itself excepted) and stays out of the means.  threshold must not be NaN.
+ * workspace (either call): at least eagcn_eval_agreement_workspace_bytes(rows, T) bytes, 8-byte aligned, contents irrelevant on entry
+ * (every word that is read is written by the call before); with tiles = ceil(rows / 256) and chunks = ceil(rows / 1024) that is
+ *     T * tiles * (min(chunks, 8) * 256 * 20 + 128)        (0 for rows < 1 or T < 1)
+ * -- per task and tile of 256 entries one 128-byte record and, per share of the rows (at most 8 workgroups share them), five 32-bit
+ * counts per entry.  eagcn_eval_agreement_splits: how many workgroups share a tile's rows in the pair kernel at that shape (1: each
+ * lane walks all rows and forms a, b itself; more: the finalize forms them from the summed counts).  rows < 2^31, T <= 65535. */
+size_t eagcn_eval_agreement_workspace_bytes(int64_t rows, int T);
+int eagcn_eval_agreement_splits(int64_t rows, int T);
+int eagcn_eval_reg_agreement(const float* scores, const float* targets, const uint8_t* valid, int64_t rows, int T, void* workspace,
+                             size_t workspace_bytes, double* out, void* stream);
+int eagcn_eval_class_threshold(const float* scores, const float* targets, const uint8_t* valid, int64_t rows, int T, float threshold,
+                               void* workspace, size_t workspace_bytes, double* out, void* stream);
 
 /* ---- atom-representation dump (train.py:213-287) on the device: the rows of the last layer's output whose sub-type lies in the closed
  * range [lo, hi] (1 .. 18 in the reference, train.py:265), appended behind a DEVICE row counter.  Two launches, no host read.
